@@ -2,6 +2,11 @@
 """bench.py — proofs/hour of the sgx_dcap_verifier k=19 prover on MI355X (BASELINE.json configs[1]) and, as extras, the
 BN254 MSM Mscalar/s at 2^24 (configs[2]) and batched NTT (configs[3]).
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the roofline of the
+HIP events inside the timed region).  Everything else described below — the host-witness rates, the other census, configs[0], one proof
+alone, the microbenchmarks, the integration rungs, the CPU leg with its verify_proof, the N > 1 extras — runs only with `--full`.  `--dump-outputs DIR`
+writes what the last timed step returned: the proof bytes of every context (opmix: its commitments as 16-bit words), as exact float32 arrays.
+
 Default (`--mode prove`): a "step" is one batch of `--inflight` (4) REAL proofs — `zk_plonk_create_proof` (the library's C++ create_proof, csrc/prover.hip;
 `--prover python`: its twin zk-dcap-verifier_amd/plonk/prover.py, same bytes), one context + HIP stream + host thread per proof in flight; the K timed steps are
 a continuous pipeline (every thread proves K proofs back to back, no join between steps; barrier + synchronize on both sides of the K steps) — over a satisfiable synthetic circuit with the census of the sgx circuit at
@@ -157,10 +162,10 @@ class ProofWorkload:
         # (all columns of a phase are committed before the next challenge is squeezed):
         nA, nP, nL = self.A, self.P, self.L
         adv, zs, lk = self.cols[:nA], self.cols[nA:nA + nP], self.cols[nA + nP:]
-        be.msm_batch(self.g_lagrange, adv, n)                           # phase 2: advice columns
-        be.msm_batch(self.g_lagrange, lk[nL:3 * nL], n)                 # phase 3: permuted input / table of every lookup
-        be.msm_batch(self.g_lagrange, zs + lk[:nL], n)                  # phase 4: permutation and lookup grand products
-        be.msm(self.g, self.hpoly, n)                                   # phase 5: vanishing argument's random poly
+        com = [be.msm_batch(self.g_lagrange, adv, n),                   # phase 2: advice columns
+               be.msm_batch(self.g_lagrange, lk[nL:3 * nL], n),         # phase 3: permuted input / table of every lookup
+               be.msm_batch(self.g_lagrange, zs + lk[:nL], n),          # phase 4: permutation and lookup grand products
+               be.msm(self.g, self.hpoly, n)]                           # phase 5: vanishing argument's random poly
         # phase 6: lagrange -> coeff -> extended coset
         for c, w in zip(self.cols, self.work):
             be.fr_scale_dev(c, self.scal[0], w, n)                      # per-proof copy (blinding changes every proof)
@@ -176,10 +181,11 @@ class ProofWorkload:
         # phase 7: h = numerator / (X^n - 1), back to coefficients, commit the d-1 pieces
         be.divide_by_vanishing_poly_dev(self.h_ext, k, ek)
         be.extended_to_coeff_dev(self.h_ext, k, ek)
-        be.msm_batch(self.g, [self.h_ext.ptr + i * n * 32 for i in range(self.d - 1)], n)
+        com.append(be.msm_batch(self.g, [self.h_ext.ptr + i * n * 32 for i in range(self.d - 1)], n))
         # phase 9: SHPLONK h(X) and linearisation commitments
-        be.msm(self.g, self.work[0], n)
-        be.msm(self.g, self.work[1], n)
+        com.append(be.msm(self.g, self.work[0], n))
+        com.append(be.msm(self.g, self.work[1], n))
+        self.commitments = np.concatenate([c.reshape(-1, 12) for c in com])      # (what a caller receives: the step's normalised G1 points)
 
 
 
@@ -588,6 +594,25 @@ def msm_microbench(be, log_n, seed, reps=3, verify=False):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, mode, wls):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float32 arrays in which every value is exact (bytes or 16-bit words).
+    prove: `proof_<i>.npy` = the proof bytes context i produced; opmix: `commitments_<i>.npy` = context i's commitments (normalised G1, 12 limbs) as 48 words each."""
+    arrays = {}
+    for i, w in enumerate(wls):
+        if mode == "prove":
+            arrays[f"proof_{i}"] = np.frombuffer(w.proof, dtype=np.uint8).astype(np.float32)
+        else:
+            c = np.ascontiguousarray(w.commitments, dtype="<u8")
+            arrays[f"commitments_{i}"] = c.view("<u2").astype(np.float32).reshape(c.shape[0], -1)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def fr_mont_limbs(x):
     return np.array([(((x % R_MOD) << 256) % R_MOD >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
@@ -641,13 +666,21 @@ def main(argv=None):
     ap.add_argument("--degree", type=int, default=5)
     ap.add_argument("--mode", choices=("prove", "opmix"), default="prove", help="prove: real create_proof over the sgx-shaped circuit (default); opmix: the hot-path call list over synthetic columns")
     ap.add_argument("--census", choices=("chip_estimate", "reference_exact"), default="chip_estimate",
-                    help="which synthetic circuit `value` is measured on (tools/sgx_shaped_circuit.py); the other one is measured as extra.census_* unless --no-extras")
+                    help="which synthetic circuit `value` is measured on (tools/sgx_shaped_circuit.py); with --full the other one is measured as extra.census_* unless --no-extras")
     ap.add_argument("--prover", choices=("native", "python"), default="native",
                     help="which create_proof the timed steps run: the library's C++ one (zk_plonk_create_proof) or its Python twin (plonk.create_proof); same bytes")
     ap.add_argument("--no-jit", action="store_true", help="the headline key's quotient on the micro-op interpreter instead of kernels generated for its program (tune quot_jit)")
     ap.add_argument("--inflight", type=int, default=4, help="proofs processed concurrently per step on one GPU (one context + HIP stream each)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the MSM 2^24 / NTT 2^22 microbenchmarks and the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: witness in host memory, the other census, BASELINE configs[0], one proof alone, "
+                         "MSM / NTT microbenchmarks, the integration rungs, the CPU baseline with verify_proof, the N > 1 extras.  Off: the run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip all of it except the pinned host-witness rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, every value exact): prove mode the proof bytes of every "
+                         "context, opmix mode every context's commitments as 16-bit words")
     args = ap.parse_args(argv)
+    extras = args.full and not args.no_extras
 
     global PROVER
     PROVER = args.prover
@@ -749,6 +782,8 @@ def main(argv=None):
     step_all(args.steps)
     barrier()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.mode, wls)
     def tsum(label):
         ms = n = 0
         for b in bes:
@@ -869,7 +904,7 @@ def main(argv=None):
         kline("quotient (kernels generated for the key's program)" if args.mode == "prove" and quotient_executor["generated_kernels"] else "quotient_kernel",
               be_stats["quotient_alg_bytes"], q_ms or 0.0, q_n, per_unit="(columns + 1) x 32 B per evaluated row")]
 
-    if args.mode == "prove":
+    if args.mode == "prove" and args.full:
         # The same K steps once more with the witness starting in HOST memory (what the Rust boundary hands over: create_proof receives host-owned
         # circuits, sgx_dcap_verifier.rs:814-822): 25 advice columns = n * 32 B each cross PCIe inside every proof, from page-locked staging
         # memory (zk_host_alloc) and, with extras, from ordinary pageable arrays.  `value` stays the HBM-resident figure (bench contract); these
@@ -890,7 +925,7 @@ def main(argv=None):
         extra["host_witness"] = dict(host_rates, bytes_per_proof=wl.A * wl.n * 32,
                                      what="same steps with the advice columns starting in host memory: every proof uploads its columns first (one zk_dev_upload_batch, the proofs in "
                                           "flight take turns on the link), then create_proof runs on the device copies; the upload of one proof overlaps the kernels of the others")
-    if args.mode == "prove" and not args.no_extras and world == 1:
+    if args.mode == "prove" and extras and world == 1:
         # The OTHER census of the synthetic circuit, same K steps, same contexts: "reference_exact" builds the base64 part exactly as
         # the reference configures and assigns it (15 advice columns that are zero outside 1696 rows, 7 lookups of 4/5 expressions on 65-/257-row
         # tables) next to the chip estimate; "chip_estimate" guesses every column.  The real circuit's cost lies wherever its un-vendored chips put it.
@@ -927,7 +962,7 @@ def main(argv=None):
                 w_.pk.release()
         except Exception as e:
             extra["census_" + other + "_error"] = repr(e)
-    if args.mode == "prove" and not args.no_extras and world == 1:
+    if args.mode == "prove" and extras and world == 1:
         # BASELINE configs[0]: the shape of the reference's stack-B circuit (crates/p256-ecdsa, k = 18, snark-verifier's Poseidon transcript: base.rs:200-212) — the case the
         # reference itself runs on the CPU.  Degree 4: three h pieces, so the key holds three cosets of its columns and h(X) comes from zk_cosets_to_pieces_dev.
         try:
@@ -958,7 +993,7 @@ def main(argv=None):
             params_b.release()
         except Exception as e:
             extra["cfg1_p256_k18_error"] = repr(e)
-    if args.mode == "prove" and not args.no_extras:
+    if args.mode == "prove" and extras:
         # latency of ONE proof with the GPU to itself (the timed region above measures throughput with several in flight)
         lat = []
         for _ in range(2):
@@ -1026,7 +1061,7 @@ def main(argv=None):
     cpu = None
     ntt_checks = []
     census2 = locals().get("census2")
-    if rank == 0 and not args.no_extras and world == 1:
+    if rank == 0 and extras and world == 1:
         try:
             extra["msm_2^20"] = msm_microbench(be, 20, 20241008, verify=True)
             extra["msm_2^21"] = msm_microbench(be, 21, 20241012, verify=True)      # the size of BASELINE configs[4]: the N = 1 point of extra.msm_sharded_2^21's curve
@@ -1110,7 +1145,7 @@ def main(argv=None):
     def multi_gpu_extras():
         if tdev == "cuda":
             torch.cuda.set_device(local)                       # the current device is per host thread
-        if world > 1 and not args.no_extras:
+        if world > 1 and extras:
             # MSM with the base table sharded over the ranks (SURVEY 8d cfg 5 / 8e): rank g holds bases and scalars
             # [g*N/G, (g+1)*N/G); the 128-byte XYZZ partials are all-gathered over RCCL/xGMI and summed on every rank.
             sizes = [int(x) for x in os.environ.get("ZK_BENCH_SHARDED_LOG_N", "21,24").split(",")]
@@ -1160,7 +1195,7 @@ def main(argv=None):
                 except Exception as e:
                     extra[f"msm_sharded_2^{logn}_error"] = str(e)
 
-        if world > 1 and not args.no_extras and args.mode == "prove":
+        if world > 1 and extras and args.mode == "prove":
             # ONE proof spread over the ranks (BASELINE configs[4] / SURVEY 8e): both SRS tables sharded by index range, every commitment of
             # create_proof = per-rank partial MSMs + one all_gather of 128-byte points; everything else is computed redundantly on every rank.
             try:
@@ -1222,7 +1257,7 @@ def main(argv=None):
     # The N > 1 extras are the only collectives of a run that no earlier round could exercise on real RCCL: they run under a watchdog so that a rank that
     # raises (or a collective that never completes) costs the extras, not the bench line — `value` above is already measured.
     multi_hung = False
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         th_multi = threading.Thread(target=multi_gpu_extras, daemon=True)
         th_multi.start()
         th_multi.join(float(os.environ.get("ZK_BENCH_MULTI_TIMEOUT", "300")))

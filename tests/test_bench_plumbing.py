@@ -56,7 +56,7 @@ def test_bench_prove_mode_emits_verified_proof(built, capsys, monkeypatch):
     monkeypatch.setattr(z.Backend, "__init__", small_init)
     monkeypatch.setattr(bench, "msm_microbench", lambda *a, **k: {"skipped": "plumbing test"})
     monkeypatch.setattr(bench, "PLUMBING_SKIP_NTT22", True, raising=False)
-    bench.main(["--steps", "1", "--warmup", "0", "--k", "6", "--inflight", "1"])
+    bench.main(["--steps", "1", "--warmup", "0", "--k", "6", "--inflight", "1", "--full"])
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert line["config"]["mode"] == "prove" and line["unit"] == "proofs/hour"
     assert line["cpu_baseline"]["verify_proof"]["accepted"] is True
@@ -74,6 +74,57 @@ def test_bench_prove_mode_emits_verified_proof(built, capsys, monkeypatch):
         assert pb[rung]["same_bytes_as_the_resident_prover"] is True and pb[rung]["proofs_per_hour"] > 0 and pb[rung]["pcie_bytes_down"] > 0, pb[rung]
     assert pb["host_columns"]["pcie_bytes_up"] > pb["host_columns_with_device_cache"]["pcie_bytes_up"]
 
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(built, capsys, monkeypatch, tmp_path):
+    """A plain run (no --full) sets up, warms up, times exactly --steps steps and prints the line: no extras, no CPU leg.  --dump-outputs writes
+    the proof bytes of the last timed step as exact float32 arrays; the same arguments give the same arrays again, also under --full."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import zk_dcap_verifier_amd as z
+    import bench
+    import sgx_shaped_circuit as sgx
+    monkeypatch.setattr(z._lib, "LIB_PATH", EMU_SO)
+    monkeypatch.setenv("ZK_BENCH_PLUMBING_TEST", "1")
+    for name, val in (("N_GATE_COLS", 2), ("N_LOOKUP_COLS", 2), ("N_FIXED", 7), ("N_GATES", 3)):
+        monkeypatch.setattr(sgx, name, val)
+    real_init = z.Backend.__init__
+
+    def small_init(self, device=0, lib_path=None):
+        real_init(self, device, lib_path)
+        self.tune(msm_sort_threads=32, msm_sort_wgs=2, msm_block=32, ntt_threads=32, ntt_tile_log=6, ntt_max_radix_log=4,
+                  msm_target_threads=64, msm_min_chunk=2, vec_block=32, quot_threads=32)
+    monkeypatch.setattr(z.Backend, "__init__", small_init)
+    monkeypatch.setattr(bench, "msm_microbench", lambda *a, **k: {"skipped": "plumbing test"})
+    monkeypatch.setattr(bench, "PLUMBING_SKIP_NTT22", True, raising=False)
+    calls = []
+    real_step = bench.ProverWorkload.step
+
+    def counted_step(self, *a, **k):
+        calls.append(k.get("witness", "resident"))
+        return real_step(self, *a, **k)
+    monkeypatch.setattr(bench.ProverWorkload, "step", counted_step)
+    argv = ["--steps", "3", "--warmup", "1", "--k", "6", "--inflight", "2"]
+
+    def run(*more):
+        calls.clear()
+        bench.main(argv + list(more))
+        return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    line = run("--dump-outputs", str(tmp_path / "a"))
+    assert len(calls) == 2 * (1 + 3) and set(calls) == {"resident"}, calls        # two contexts x (warmup + timed steps), nothing after them
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "proofs/hour"
+    assert line["cpu_baseline"] is None
+    assert not {"host_witness", "single_proof", "thin_shim", "phase_batched_shim", "cfg1_p256_k18"} & set(line["extra"]), line["extra"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["proof_0.npy", "proof_1.npy"]
+    a = [np.load(tmp_path / "a" / f"proof_{i}.npy") for i in range(2)]
+    assert all(x.dtype == np.float32 and x.ndim == 1 and x.size > 0 for x in a)
+    assert (a[0].astype(np.uint8) == a[0]).all() and (a[0] == a[1]).all()                      # bytes; both contexts prove the same witness with the same draws
+    run("--dump-outputs", str(tmp_path / "b"))
+    assert all((np.load(tmp_path / "b" / f"proof_{i}.npy") == a[i]).all() for i in range(2))
+    line = run("--full", "--no-extras", "--dump-outputs", str(tmp_path / "c"))                   # more proofs follow the timed steps here: the dump is of the timed ones
+    assert "pinned" in line["extra"]["host_witness"] and len(calls) > 2 * (1 + 3)
+    assert all((np.load(tmp_path / "c" / f"proof_{i}.npy") == a[i]).all() for i in range(2))
 
 def _bench_rank(rank, world, port, out_dir):
     import io
@@ -94,7 +145,7 @@ def _bench_rank(rank, world, port, out_dir):
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main(["--mode", "opmix", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--k", "4", "--advice", "2", "--fixed", "2", "--lookups", "1",
-                    "--perm-columns", "2", "--degree", "4"])
+                    "--perm-columns", "2", "--degree", "4", "--full"])
     open(os.path.join(out_dir, f"rank{rank}.txt"), "w").write(buf.getvalue())
 
 
@@ -132,7 +183,7 @@ def _bench_rank_prove(rank, world, port, out_dir):
     z.Backend.__init__ = small_init
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "0", "--k", "6", "--inflight", "1"])
+        bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "0", "--k", "6", "--inflight", "1", "--full"])
     open(os.path.join(out_dir, f"rank{rank}.txt"), "w").write(buf.getvalue())
 
 

@@ -6,7 +6,7 @@ TAG=$1
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/${TAG}_bench_default.json 2> $O/bench.err
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 bench.py --steps 3 --warmup 1 --no-extras > $O/${TAG}_bench_under_rocprofv3.json 2>> $O/bench.err
 # (one proof at a time with the side lane OFF: the per-kernel tables and counters below are of kernels that run alone, not beside the helper context's transforms)
 export ZK_TUNE=prover_side_lane=0
