@@ -71,7 +71,7 @@ def _check_backend(be, orc, pyref, k, count, seed, bf=5):
     want_l = orc.lookup_product(vals[0], sig[0], vals[-1], sig[-1], k, beta, gamma, blind)
     be.lookup_product_dev(dv[0], ds[0], dv[-1], ds[-1], k, beta, gamma, blind, dz)
     assert (dz.download((n, 4)) == want_l).all()
-    # every lookup of a proof in one call (k >= 11 takes the batched launch sequence, smaller domains the per-lookup one)
+    # every lookup of a proof in one call (the same launch sequence as the single forms above, with three columns; k < 11: a column is less than one scan span)
     quads = [(dv[0], ds[0], dv[-1], ds[-1]), (ds[0], dv[0], ds[-1], dv[-1]), (dv[-1], ds[-1], dv[0], ds[0])]
     hq = [(vals[0], sig[0], vals[-1], sig[-1]), (sig[0], vals[0], sig[-1], vals[-1]), (vals[-1], sig[-1], vals[0], sig[0])]
     blinds = [pc.rand_fr(orc, pyref, bf, seed + 40 + j) for j in range(3)]
@@ -82,12 +82,12 @@ def _check_backend(be, orc, pyref, k, count, seed, bf=5):
         d.free()
 
 
-@pytest.mark.parametrize("k,count", [(3, 1), (5, 3), (9, 2), (12, 4)])
+@pytest.mark.parametrize("k,count", [(3, 1), (5, 3), (9, 2), (11, 2), (12, 4)])
 def test_emulated_grand_products(emu, orc, pyref, k, count):
     _check_backend(emu, orc, pyref, k, count, seed=10 * k + count)
 
 
-@pytest.mark.parametrize("k", [5, 12])     # 12: the all-sets-in-one-launch path (domains of at least one scan span), 5: set by set
+@pytest.mark.parametrize("k", [5, 11, 12])     # all sets in one launch sequence; 5: partial scan spans, 11: one span per column, 12: two
 def test_permutation_commit_chains_sets(emu, orc, pyref, k):
     """permutation_commit(): z of set s starts at the last unblinded value of set s-1, delta powers continue."""
     cs_degree, ncols, bf = 4, 5, 5

@@ -20,7 +20,7 @@ def _case(orc, pyref, k, seed, kind):
         tab_vals = [rnd.randrange(R) for _ in range(u)]
         inp_vals = [rnd.choice(tab_vals[: max(2, u // 2)]) for _ in range(u)]
     elif kind == "window_ties":              # full-width keys that agree on the top 64 bits in use and differ far below: the 64-bit window
-        big = (1 << 252) + (0x1234567 << 200)  # sort cannot order them, the order check must send the call down the every-digit path
+        big = (1 << 252) + (0x1234567 << 200)  # sort cannot order them, the order check must send the column through the refinement
         tab_vals = [big + rnd.randrange(1 << 40) for _ in range(u)]
         inp_vals = [rnd.choice(tab_vals[: max(2, u // 2)]) for _ in range(u)]
     elif kind == "theta_last":               # theta-compressed tuples whose LAST expression differs (the base64 lookups of the sgx circuit,
@@ -110,9 +110,9 @@ def test_lookup_permute_rejects_value_outside_table(emu, orc, pyref):
 def test_gpu_lookup_permute(gpu, orc, pyref, k, kind):
     gpu.timing(True)
     _check(gpu, orc, pyref, k, kind, seed=k)
-    if kind in ("theta_last", "two_stage_ties", "window_ties"):       # window ties are refined by a few extra radix passes, not re-sorted digit by digit
+    if kind in ("theta_last", "two_stage_ties", "window_ties"):       # window ties are refined by a few extra radix passes over the tie mask's bits
         # (refined the first time a shape is seen; afterwards the context remembers which columns tie and sorts them in two stages straight away)
-        assert gpu.stat_get("lookup_generic_sorts") == 0 and gpu.stat_get("lookup_refined_sorts") + gpu.stat_get("lookup_hinted_sorts") >= 1
+        assert gpu.stat_get("lookup_refined_sorts") + gpu.stat_get("lookup_hinted_sorts") >= 1
     gpu.timing(False)
 
 
@@ -122,20 +122,10 @@ def test_emulated_lookup_permute_refines_window_ties(emu, orc, pyref, kind):
     try:
         emu.timing(True)
         _check(emu, orc, pyref, 9, kind, seed=3)
-        assert emu.stat_get("lookup_generic_sorts") == 0 and emu.stat_get("lookup_refined_sorts") + emu.stat_get("lookup_hinted_sorts") >= 1
+        assert emu.stat_get("lookup_refined_sorts") + emu.stat_get("lookup_hinted_sorts") >= 1
     finally:
         emu.timing(False)
         emu.tune(vec_block=32)
-
-
-@pytest.mark.gpu
-def test_gpu_lookup_permute_generic_sort_path(gpu, orc, pyref):
-    """the every-digit sort (taken when rows tie on the 64-bit window) forced on ordinary full-width data: same answer"""
-    gpu.tune(lookup_force_generic_sort=1)
-    try:
-        _check(gpu, orc, pyref, 12, "wide", seed=5)
-    finally:
-        gpu.tune(lookup_force_generic_sort=0)
 
 
 def test_emulated_lookup_tie_hint_is_only_a_hint(built, orc, pyref):
@@ -151,7 +141,7 @@ def test_emulated_lookup_tie_hint_is_only_a_hint(built, orc, pyref):
         _check(be, orc, pyref, 9, "two_stage_ties", seed=4)             # same shape, ties now differ around bits 20 and 130
         _check(be, orc, pyref, 9, "wide", seed=5)                       # no ties: the extra low passes are harmless
         _check(be, orc, pyref, 9, "theta_last", seed=6)
-        assert be.stat_get("lookup_generic_sorts") == 0 and be.stat_get("lookup_hinted_sorts") >= 1
+        assert be.stat_get("lookup_hinted_sorts") >= 1
     finally:
         be.close()
 

@@ -5,10 +5,10 @@
 //   src/plonk/lookup/prover.rs       Permuted::commit_product
 // i.e. frac[i] = numerator_i / denominator_i (batch inversion), z[0] = z_init,
 // z[i+1] = z[i] * frac[i], last `blinding_factors` rows replaced by caller-supplied randomness.
-// The CPU code is a serial scan over n rows per column set; here it is a three-phase parallel prefix
-// product (per-thread runs -> LDS scan per workgroup -> scan of workgroup totals), and the batch
-// inversion is Montgomery's trick on per-thread chunks.  Outputs feed zk_msm / zk_lagrange_to_coeff
-// directly, so the column never leaves HBM.
+// The CPU code is a serial scan over n rows per column set; here every entry point runs ONE launch sequence over a batch of columns
+// (a single set or lookup is a batch of one): fractions per column, the batch inversion over all rows (Montgomery's trick on per-thread
+// chunks), then a three-phase parallel prefix product per column (per-thread runs -> LDS scan per workgroup -> scan of workgroup totals)
+// and the assembly.  Outputs feed zk_msm / zk_lagrange_to_coeff directly, so the column never leaves HBM.
 #include "ctx.h"
 #include <algorithm>
 #include <vector>
@@ -51,13 +51,6 @@ ZK_KERNEL void gp_perm_fraction_kernel(GpPermArgs a) {
     store_u256(a.den, i, den);
 }
 // lookup: num = (compressed_input + beta)(compressed_table + gamma), den = (permuted_input + beta)(permuted_table + gamma)
-ZK_KERNEL void gp_lookup_fraction_kernel(const void* cin, const void* ctab, const void* pin, const void* ptab, uint32_t n, u256 beta, u256 gamma,
-                                         void* num, void* den) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    store_u256(num, i, Fr::mul(Fr::add(load_u256(cin, i), beta), Fr::add(load_u256(ctab, i), gamma)));
-    store_u256(den, i, Fr::mul(Fr::add(load_u256(pin, i), beta), Fr::add(load_u256(ptab, i), gamma)));
-}
 // batched: blockIdx.y = lookup; cols = [cin_0, ctab_0, pin_0, ptab_0, cin_1, ...] (device array), num / den = [l][n]
 ZK_KERNEL void gp_lookup_fraction_batch_kernel(const void* const* cols, uint32_t n, u256 beta, u256 gamma, void* num, void* den) {
     const uint32_t l = blockIdx.y;
@@ -139,9 +132,11 @@ ZK_KERNEL void gp_batch_divide_kernel(void* num, const void* den, uint32_t n, ui
     }
 }
 
-// phase A: x[i] <- inclusive prefix product inside the workgroup's span; totals[b] <- product of the span
-ZK_KERNEL void gp_scan_local_kernel(void* x, uint32_t n, void* totals) {
+// phase A: blockIdx.y = column c of x = [c][n]: x[c][i] <- inclusive prefix product inside the workgroup's span of the column
+// (a span never straddles two columns); totals[c][blockIdx.x] <- product of the span
+ZK_KERNEL void gp_scan_local_kernel(void* x_all, uint32_t n, void* totals) {
     const uint32_t span = blockDim.x * GP_E;
+    void* x = (char*)x_all + (size_t)blockIdx.y * n * 32;
     const uint32_t base = blockIdx.x * span + threadIdx.x * GP_E;
     u256 v[GP_E];
     u256 run = Fr::one();
@@ -156,9 +151,9 @@ ZK_KERNEL void gp_scan_local_kernel(void* x, uint32_t n, void* totals) {
 #pragma unroll
     for (uint32_t e = 0; e < GP_E; e++)
         if (base + e < n) store_u256(x, base + e, Fr::mul(v[e], excl));
-    if (threadIdx.x == 0) store_u256(totals, blockIdx.x, total);
+    if (threadIdx.x == 0) store_u256(totals, (size_t)blockIdx.y * gridDim.x + blockIdx.x, total);
 }
-// phase B (single workgroup): totals[b] <- exclusive prefix product of the workgroup totals
+// phase B (one workgroup per column): totals[c][b] <- exclusive prefix product of the column's workgroup totals
 ZK_KERNEL void gp_scan_totals_kernel(void* totals_all, uint32_t nblocks) {
     void* totals = (char*)totals_all + (size_t)blockIdx.x * nblocks * 32;      // one workgroup per column of a batch
     const uint32_t per = (nblocks + blockDim.x - 1) / blockDim.x;
@@ -173,22 +168,8 @@ ZK_KERNEL void gp_scan_totals_kernel(void* totals_all, uint32_t nblocks) {
         acc = Fr::mul(acc, t);
     }
 }
-// phase C: z[0] = init; z[i+1] = init * blockprefix * local[i]  (i + 1 < n_keep); rows >= n_keep take the blinding values
-ZK_KERNEL void gp_assemble_kernel(const void* local, const void* block_prefix, uint32_t n, uint32_t n_keep, u256 init, const void* blinding, void* z) {
-    const uint32_t span = GP_T * GP_E;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // output row
-    if (i >= n) return;
-    u256 o;
-    if (i >= n_keep) o = load_u256(blinding, i - n_keep);
-    else if (i == 0) o = init;
-    else {
-        const uint32_t src = (uint32_t)i - 1;
-        o = Fr::mul(Fr::mul(load_u256(local, src), load_u256(block_prefix, src / span)), init);
-    }
-    store_u256(z, i, o);
-}
-
-// batched phase C: blockIdx.y = column; local / block_prefix / z are [col][..]; inits: per-column Montgomery scalars (device); blinding [col][bf]
+// phase C: blockIdx.y = column; z[0] = init; z[i+1] = init * blockprefix * local[i]  (i + 1 < n_keep), rows >= n_keep take the blinding values;
+// local / block_prefix / z are [col][..]; inits: per-column Montgomery scalars (device); blinding [col][bf]
 ZK_KERNEL void gp_assemble_batch_kernel(const void* local, const void* block_prefix, uint32_t n, uint32_t n_keep, const void* inits, const void* blinding,
                                         uint32_t bf, void* const* zs, uint32_t nblocks) {
     const uint32_t span = GP_T * GP_E, c = blockIdx.y;
@@ -206,27 +187,93 @@ ZK_KERNEL void gp_assemble_batch_kernel(const void* local, const void* block_pre
 }
 
 // ---- host ------------------------------------------------------------------------------------------
-static int gp_finish(zk_ctx* ctx, void* d_frac, void* d_den_scratch, void* d_aux, uint32_t n, const u256& init, const void* h_blinding, uint32_t bf,
-                     void* d_z, void* h_last_z) {
+static u256 gp_rd(const void* p) { u256 o; memcpy(&o, p, 32); return o; }
+
+// The grand products of `count` columns of n rows in one launch sequence.  fractions(num, den, extra) launches the kernels that fill num / den
+// ([column][n]; extra: `extra_bytes` of device workspace for them); then ONE batch division over all count * n rows (the inversion's Fermat chain
+// per workgroup is paid once, not once per column), the prefix products of every column, and the assembly.  chain: the columns are the sets of
+// one permutation argument, z_s[0] = z_(s-1)[n - bf - 1] with the first set at init — every set is scanned from 1, the few chaining products are
+// done on the host from two downloaded values per set, and the assemble pass applies them; otherwise every column starts at init.
+// blinding: count x bf x 32 B; h_last_z (optional) <- z[n - bf - 1] of the last column.  Needs bf + 2 <= n.
+template <class Fractions>
+static int gp_products(zk_ctx* ctx, size_t count, uint32_t n, const u256& init, bool chain, const void* blinding, uint32_t bf, void* const* d_zs, void* h_last_z,
+                       size_t extra_bytes, Fractions fractions) {
+    const uint32_t span = GP_T * GP_E, nblocks = (n + span - 1) / span;     // scan workgroups per column
+    const size_t N = count * (size_t)n;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_num = take(N * 32), o_den = take(N * 32), o_scr = take(N * 32), o_tot = take(count * nblocks * 32), o_bl = take(count * (size_t)(bf + 1) * 32),
+                 o_in = take(count * 32), o_zp = take(count * sizeof(void*)), o_ex = take(extra_bytes);
+    ZK_HIP(ctx->ws_tmp.ensure(off + 256));
+    char* base = (char*)ctx->ws_tmp.p;
     hipStream_t st = ctx->stream;
     const int blk = ctx->tune.vec_block;
+    int rc = fractions(base + o_num, base + o_den, base + o_ex);
+    if (rc) return rc;
+    ZK_HIP(hipMemcpyAsync(base + o_zp, d_zs, count * sizeof(void*), hipMemcpyHostToDevice, st));
+    if (bf) ZK_HIP(hipMemcpyAsync(base + o_bl, blinding, count * (size_t)bf * 32, hipMemcpyHostToDevice, st));
     const uint32_t chunk = 32;
     const int dblk = std::min<int>(ctx->tune.vec_block, (int)GP_T);   // the division kernel scans over its workgroup in LDS arrays of GP_T entries
-    ZK_LAUNCH(gp_batch_divide_kernel, (uint32_t)(((n + chunk - 1) / chunk + dblk - 1) / dblk), dblk, 0, st, d_frac, (const void*)d_den_scratch, n, chunk, d_aux);
+    ZK_LAUNCH(gp_batch_divide_kernel, (uint32_t)(((N + chunk - 1) / chunk + dblk - 1) / dblk), dblk, 0, st, (void*)(base + o_num), (const void*)(base + o_den), (uint32_t)N, chunk,
+              (void*)(base + o_scr));
     ZK_CHECK_LAUNCH();
-    const uint32_t span = GP_T * GP_E, nblocks = (n + span - 1) / span;
-    void* d_tot = (char*)d_aux;                       // scratch is free again after the division
-    ZK_LAUNCH(gp_scan_local_kernel, nblocks, GP_T, 0, st, d_frac, n, d_tot);
+    ZK_LAUNCH(gp_scan_local_kernel, dim3(nblocks, (uint32_t)count), GP_T, 0, st, (void*)(base + o_num), n, (void*)(base + o_tot));
     ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_scan_totals_kernel, 1, GP_T, 0, st, d_tot, nblocks);
+    ZK_LAUNCH(gp_scan_totals_kernel, (uint32_t)count, GP_T, 0, st, (void*)(base + o_tot), nblocks);
     ZK_CHECK_LAUNCH();
-    void* d_blind = (char*)d_aux + (size_t)nblocks * 32;
-    if (bf) ZK_HIP(hipMemcpyAsync(d_blind, h_blinding, (size_t)bf * 32, hipMemcpyHostToDevice, st));
-    ZK_LAUNCH(gp_assemble_kernel, (n + blk - 1) / blk, blk, 0, st, (const void*)d_frac, (const void*)d_tot, n, n - bf, init, (const void*)d_blind, d_z);
+    std::vector<u256> inits(count, init);
+    if (chain) {
+        // P_s = prod_{j < n - bf - 1} frac_s[j] = local[src] * block_prefix[src / span], src = n - bf - 2
+        const uint32_t src = n - bf - 2;
+        std::vector<u256> loc(count), pre(count);
+        for (size_t s = 0; s < count; s++) {
+            ZK_HIP(hipMemcpyAsync(&loc[s], base + o_num + (s * (size_t)n + src) * 32, 32, hipMemcpyDeviceToHost, st));
+            ZK_HIP(hipMemcpyAsync(&pre[s], base + o_tot + (s * (size_t)nblocks + src / span) * 32, 32, hipMemcpyDeviceToHost, st));
+        }
+        ZK_HIP(hipStreamSynchronize(st));
+        for (size_t s = 1; s < count; s++) inits[s] = Fr::mul(inits[s - 1], Fr::mul(loc[s - 1], pre[s - 1]));
+    }
+    ZK_HIP(hipMemcpyAsync(base + o_in, inits.data(), count * 32, hipMemcpyHostToDevice, st));
+    ZK_LAUNCH(gp_assemble_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, st, (const void*)(base + o_num), (const void*)(base + o_tot), n, n - bf,
+              (const void*)(base + o_in), (const void*)(base + o_bl), bf, (void* const*)(base + o_zp), nblocks);
     ZK_CHECK_LAUNCH();
-    if (h_last_z) ZK_HIP(hipMemcpyAsync(h_last_z, (char*)d_z + (size_t)(n - bf - 1) * 32, 32, hipMemcpyDeviceToHost, st));
+    if (h_last_z) ZK_HIP(hipMemcpyAsync(h_last_z, (char*)d_zs[count - 1] + (size_t)(n - bf - 1) * 32, 32, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
     return ZK_OK;
+}
+
+// The permutation argument (permutation::Argument::commit's loop over chunks): m columns in sets of chunk_len; the delta powers continue across the
+// sets from delta_start (the first column's), z of the first set starts at z_init.  The callers have checked the arguments.
+static int gp_permutation(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
+                          const void* gamma, const u256& delta_start, const u256& z_init, const void* blinding, uint32_t bf, void* const* d_zs, void* h_last_z) {
+    const uint32_t n = 1u << k;
+    const size_t n_sets = (m + chunk_len - 1) / chunk_len;
+    const uint64_t dl[4] = BN254_FR_DELTA_M;
+    u256 delta;
+    for (int i = 0; i < 8; i++) delta.v[i] = (uint32_t)(dl[i >> 1] >> (32 * (i & 1)));
+    GpPermArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.beta = gp_rd(beta); a.gamma = gp_rd(gamma);
+    int rc = ntt_pow_tables(ctx, k, domain_omega(k), &a.tw_lo, &a.tw_hi, &a.lo_bits);
+    if (rc) return rc;
+    const int blk = ctx->tune.vec_block;
+    return gp_products(ctx, n_sets, n, z_init, true, blinding, bf, d_zs, h_last_z, 0, [&](char* num, char* den, char*) -> int {
+        u256 cur = Fr::mul(delta_start, a.beta);                     // delta^j * beta, continuing across the sets
+        for (size_t s = 0; s < n_sets; s++) {
+            const size_t lo = s * chunk_len, cnt = std::min<size_t>(chunk_len, m - lo);
+            a.count = (uint32_t)cnt;
+            for (size_t j = 0; j < cnt; j++) {
+                a.values[j] = values[lo + j]; a.sigmas[j] = sigmas[lo + j];
+                a.delta_beta[j] = cur;
+                cur = Fr::mul(cur, delta);
+            }
+            a.num = num + s * (size_t)n * 32;
+            a.den = den + s * (size_t)n * 32;
+            ZK_LAUNCH(gp_perm_fraction_kernel, (n + blk - 1) / blk, blk, 0, ctx->stream, a);
+            ZK_CHECK_LAUNCH();
+        }
+        return ZK_OK;
+    });
 }
 
 int permutation_product(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t count, uint32_t k, const void* beta, const void* gamma,
@@ -237,52 +284,26 @@ int permutation_product(zk_ctx* ctx, const void* const* values, const void* cons
     if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_dev: k = %u out of range", k);
     const uint32_t n = 1u << k;
     if (bf + 1 >= n) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_dev: blinding_factors too large");
-    auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    GpPermArgs a;
-    memset(&a, 0, sizeof a);
-    a.count = (uint32_t)count; a.n = n; a.beta = rd(beta); a.gamma = rd(gamma);
-    const uint64_t dl[4] = BN254_FR_DELTA_M;
-    u256 delta;
-    for (int i = 0; i < 8; i++) delta.v[i] = (uint32_t)(dl[i >> 1] >> (32 * (i & 1)));
-    u256 cur = Fr::mul(rd(delta_start), a.beta);
-    for (size_t j = 0; j < count; j++) {
+    for (size_t j = 0; j < count; j++)
         if (!values[j] || !sigmas[j]) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_dev: null column %zu", j);
-        a.values[j] = values[j]; a.sigmas[j] = sigmas[j];
-        a.delta_beta[j] = cur;
-        cur = Fr::mul(cur, delta);
-    }
-    int rc = ntt_pow_tables(ctx, k, domain_omega(k), &a.tw_lo, &a.tw_hi, &a.lo_bits);
-    if (rc) return rc;
-    ZK_HIP(ctx->ws_tmp.ensure((size_t)n * 96 + (size_t)(n / (GP_T * GP_E) + 2 + bf) * 32 + 4096));
-    a.num = ctx->ws_tmp.p;
-    a.den = (char*)ctx->ws_tmp.p + (size_t)n * 32;
-    void* d_aux = (char*)ctx->ws_tmp.p + (size_t)n * 64;
-    const int blk = ctx->tune.vec_block;
-    ZK_LAUNCH(gp_perm_fraction_kernel, (n + blk - 1) / blk, blk, 0, ctx->stream, a);
-    ZK_CHECK_LAUNCH();
-    return gp_finish(ctx, a.num, a.den, d_aux, n, rd(z_init), blinding, bf, d_z, h_last_z);
+    return gp_permutation(ctx, values, sigmas, count, (uint32_t)count, k, beta, gamma, gp_rd(delta_start), gp_rd(z_init), blinding, bf, &d_z, h_last_z);
 }
 
-int lookup_product(zk_ctx* ctx, const void* cin, const void* ctab, const void* pin, const void* ptab, uint32_t k, const void* beta, const void* gamma,
-                   const void* blinding, uint32_t bf, void* d_z) {
-    if (!cin || !ctab || !pin || !ptab || !beta || !gamma || !d_z || (bf && !blinding)) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: null argument");
-    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: k = %u out of range", k);
+// All column sets of the permutation argument in one launch sequence.  d_zs: n_sets outputs; blinding: n_sets x bf x 32 B.
+int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
+                            const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs) {
+    if (m == 0) return ZK_OK;
+    if (!values || !sigmas || !beta || !gamma || !d_zs || (bf && !blinding) || chunk_len == 0) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null argument");
+    if (chunk_len > (uint32_t)GP_MAX_COLS) return ctx->fail(ZK_ERR_LIMIT, "zk_permutation_product_all_dev: %u columns per set (max %d)", chunk_len, GP_MAX_COLS);
+    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: k = %u out of range", k);
     const uint32_t n = 1u << k;
-    if (bf + 1 >= n) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: blinding_factors too large");
-    auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    ZK_HIP(ctx->ws_tmp.ensure((size_t)n * 96 + (size_t)(n / (GP_T * GP_E) + 2 + bf) * 32 + 4096));
-    void* num = ctx->ws_tmp.p;
-    void* den = (char*)ctx->ws_tmp.p + (size_t)n * 32;
-    void* d_aux = (char*)ctx->ws_tmp.p + (size_t)n * 64;
-    const int blk = ctx->tune.vec_block;
-    ZK_LAUNCH(gp_lookup_fraction_kernel, (n + blk - 1) / blk, blk, 0, ctx->stream, cin, ctab, pin, ptab, n, rd(beta), rd(gamma), num, den);
-    ZK_CHECK_LAUNCH();
-    return gp_finish(ctx, num, den, d_aux, n, Fr::one(), blinding, bf, d_z, nullptr);
+    if (bf + 2 >= n) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: blinding_factors too large");
+    for (size_t j = 0; j < m; j++)
+        if (!values[j] || !sigmas[j]) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null column %zu", j);
+    return gp_permutation(ctx, values, sigmas, m, chunk_len, k, beta, gamma, Fr::one(), Fr::one(), blinding, bf, d_zs, nullptr);
 }
 
-
-// All lookup grand products of a proof in one launch sequence (Permuted::commit_product for every lookup): the batch
-// inversion's one Fermat chain per thread is paid once, not once per lookup.  Needs n to be a multiple of the scan span.
+// All lookup grand products of a proof in one launch sequence (Permuted::commit_product for every lookup); cols4 = [cin, ctab, pin, ptab] per lookup.
 int lookup_product_batch(zk_ctx* ctx, const void* const* cols4, size_t count, uint32_t k, const void* beta, const void* gamma, const void* blinding,
                          uint32_t bf, void* const* d_zs) {
     if (count == 0) return ZK_OK;
@@ -292,140 +313,25 @@ int lookup_product_batch(zk_ctx* ctx, const void* const* cols4, size_t count, ui
     if (bf + 1 >= n) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_batch_dev: blinding_factors too large");
     for (size_t i = 0; i < 4 * count; i++) if (!cols4[i]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_batch_dev: null column");
     for (size_t i = 0; i < count; i++) if (!d_zs[i]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_batch_dev: null output");
-    auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    const uint32_t span = GP_T * GP_E;
-    if (n % span) {   // tiny domains: the scan spans would straddle columns
-        for (size_t l = 0; l < count; l++) {
-            int rc = lookup_product(ctx, cols4[4 * l], cols4[4 * l + 1], cols4[4 * l + 2], cols4[4 * l + 3], k, beta, gamma,
-                                    (const char*)blinding + l * (size_t)bf * 32, bf, d_zs[l]);
-            if (rc) return rc;
-        }
-        return ZK_OK;
-    }
-    const uint32_t nblocks = n / span;
-    const size_t N = (size_t)count * n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_num = take(N * 32), o_den = take(N * 32), o_scr = take(N * 32), o_tot = take((size_t)count * nblocks * 32), o_bl = take((size_t)count * (bf + 1) * 32),
-                 o_in = take(count * 32), o_cp = take(4 * count * sizeof(void*)), o_zp = take(count * sizeof(void*));
-    ZK_HIP(ctx->ws_tmp.ensure(off + 256));
-    char* base = (char*)ctx->ws_tmp.p;
-    hipStream_t st = ctx->stream;
+    const u256 b = gp_rd(beta), g = gp_rd(gamma);
     const int blk = ctx->tune.vec_block;
-    ZK_HIP(hipMemcpyAsync(base + o_cp, cols4, 4 * count * sizeof(void*), hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(base + o_zp, d_zs, count * sizeof(void*), hipMemcpyHostToDevice, st));
-    if (bf) ZK_HIP(hipMemcpyAsync(base + o_bl, blinding, (size_t)count * bf * 32, hipMemcpyHostToDevice, st));
-    std::vector<u256> ones(count, Fr::one());
-    ZK_HIP(hipMemcpyAsync(base + o_in, ones.data(), count * 32, hipMemcpyHostToDevice, st));
-    ZK_LAUNCH(gp_lookup_fraction_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, st, (const void* const*)(base + o_cp), n, rd(beta), rd(gamma),
-              (void*)(base + o_num), (void*)(base + o_den));
-    ZK_CHECK_LAUNCH();
-    const uint32_t chunk = 32;
-    const int dblk = std::min<int>(ctx->tune.vec_block, (int)GP_T);   // the division kernel scans over its workgroup in LDS arrays of GP_T entries
-    ZK_LAUNCH(gp_batch_divide_kernel, (uint32_t)(((N + chunk - 1) / chunk + dblk - 1) / dblk), dblk, 0, st, (void*)(base + o_num), (const void*)(base + o_den), (uint32_t)N, chunk,
-              (void*)(base + o_scr));
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_scan_local_kernel, (uint32_t)(count * nblocks), GP_T, 0, st, (void*)(base + o_num), (uint32_t)N, (void*)(base + o_tot));
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_scan_totals_kernel, (uint32_t)count, GP_T, 0, st, (void*)(base + o_tot), nblocks);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_assemble_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, st, (const void*)(base + o_num), (const void*)(base + o_tot), n, n - bf,
-              (const void*)(base + o_in), (const void*)(base + o_bl), bf, (void* const*)(base + o_zp), nblocks);
-    ZK_CHECK_LAUNCH();
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    return gp_products(ctx, count, n, Fr::one(), false, blinding, bf, d_zs, nullptr, 4 * count * sizeof(void*), [&](char* num, char* den, char* d_cols) -> int {
+        ZK_HIP(hipMemcpyAsync(d_cols, cols4, 4 * count * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+        ZK_LAUNCH(gp_lookup_fraction_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, ctx->stream, (const void* const*)d_cols, n, b, g,
+                  (void*)num, (void*)den);
+        ZK_CHECK_LAUNCH();
+        return ZK_OK;
+    });
 }
 
-
-// All column sets of the permutation argument in one launch sequence (permutation::Argument::commit's loop over chunks).  The sets
-// chain through z_s[0] = z_(s-1)[n - bf - 1]; here every set is first scanned with init = 1, the few chaining products are done on the
-// host from two downloaded values per set, and the assemble pass applies them.  d_zs: n_sets outputs; blinding: n_sets x bf x 32 B.
-int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
-                            const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs) {
-    if (m == 0) return ZK_OK;
-    if (!values || !sigmas || !beta || !gamma || !d_zs || (bf && !blinding) || chunk_len == 0) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null argument");
-    if (chunk_len > (uint32_t)GP_MAX_COLS) return ctx->fail(ZK_ERR_LIMIT, "zk_permutation_product_all_dev: %u columns per set (max %d)", chunk_len, GP_MAX_COLS);
-    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: k = %u out of range", k);
+int lookup_product(zk_ctx* ctx, const void* cin, const void* ctab, const void* pin, const void* ptab, uint32_t k, const void* beta, const void* gamma,
+                   const void* blinding, uint32_t bf, void* d_z) {
+    if (!cin || !ctab || !pin || !ptab || !beta || !gamma || !d_z || (bf && !blinding)) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: null argument");
+    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: k = %u out of range", k);
     const uint32_t n = 1u << k;
-    if (bf + 2 >= n) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: blinding_factors too large");
-    const size_t n_sets = (m + chunk_len - 1) / chunk_len;
-    auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    const uint64_t dl[4] = BN254_FR_DELTA_M;
-    u256 delta;
-    for (int i = 0; i < 8; i++) delta.v[i] = (uint32_t)(dl[i >> 1] >> (32 * (i & 1)));
-    const uint32_t span = GP_T * GP_E;
-    if (n % span) {   // tiny domains: set by set
-        u256 z_init = Fr::one(), dstart = Fr::one();
-        for (size_t sidx = 0; sidx < n_sets; sidx++) {
-            const size_t lo = sidx * chunk_len, cnt = std::min<size_t>(chunk_len, m - lo);
-            u256 last;
-            int rc = permutation_product(ctx, values + lo, sigmas + lo, cnt, k, beta, gamma, &dstart, &z_init, (const char*)blinding + sidx * (size_t)bf * 32, bf,
-                                         d_zs[sidx], &last);
-            if (rc) return rc;
-            z_init = last;
-            for (size_t j = 0; j < cnt; j++) dstart = Fr::mul(dstart, delta);
-        }
-        return ZK_OK;
-    }
-    const uint32_t nblocks = n / span;
-    const size_t N = n_sets * (size_t)n;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_num = take(N * 32), o_den = take(N * 32), o_scr = take(N * 32), o_tot = take(n_sets * nblocks * 32), o_bl = take(n_sets * (size_t)(bf + 1) * 32),
-                 o_in = take(n_sets * 32), o_zp = take(n_sets * sizeof(void*));
-    ZK_HIP(ctx->ws_tmp.ensure(off + 256));
-    char* base = (char*)ctx->ws_tmp.p;
-    hipStream_t st = ctx->stream;
-    const int blk = ctx->tune.vec_block;
-    GpPermArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = n; a.beta = rd(beta); a.gamma = rd(gamma);
-    int rc = ntt_pow_tables(ctx, k, domain_omega(k), &a.tw_lo, &a.tw_hi, &a.lo_bits);
-    if (rc) return rc;
-    ZK_HIP(ctx->ws_tmp.ensure(off + 256));     // (ntt_pow_tables may have touched other workspaces, not this one)
-    base = (char*)ctx->ws_tmp.p;
-    u256 cur = a.beta;                           // delta^j * beta, continuing across the sets
-    for (size_t sidx = 0; sidx < n_sets; sidx++) {
-        const size_t lo = sidx * chunk_len, cnt = std::min<size_t>(chunk_len, m - lo);
-        a.count = (uint32_t)cnt;
-        for (size_t j = 0; j < cnt; j++) {
-            if (!values[lo + j] || !sigmas[lo + j]) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null column %zu", lo + j);
-            a.values[j] = values[lo + j]; a.sigmas[j] = sigmas[lo + j];
-            a.delta_beta[j] = cur;
-            cur = Fr::mul(cur, delta);
-        }
-        a.num = base + o_num + sidx * (size_t)n * 32;
-        a.den = base + o_den + sidx * (size_t)n * 32;
-        ZK_LAUNCH(gp_perm_fraction_kernel, (n + blk - 1) / blk, blk, 0, st, a);
-        ZK_CHECK_LAUNCH();
-    }
-    ZK_HIP(hipMemcpyAsync(base + o_zp, d_zs, n_sets * sizeof(void*), hipMemcpyHostToDevice, st));
-    if (bf) ZK_HIP(hipMemcpyAsync(base + o_bl, blinding, n_sets * (size_t)bf * 32, hipMemcpyHostToDevice, st));
-    const uint32_t chunk = 32;
-    const int dblk = std::min<int>(ctx->tune.vec_block, (int)GP_T);   // the division kernel scans over its workgroup in LDS arrays of GP_T entries
-    ZK_LAUNCH(gp_batch_divide_kernel, (uint32_t)(((N + chunk - 1) / chunk + dblk - 1) / dblk), dblk, 0, st, (void*)(base + o_num), (const void*)(base + o_den), (uint32_t)N, chunk,
-              (void*)(base + o_scr));
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_scan_local_kernel, (uint32_t)(n_sets * nblocks), GP_T, 0, st, (void*)(base + o_num), (uint32_t)N, (void*)(base + o_tot));
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(gp_scan_totals_kernel, (uint32_t)n_sets, GP_T, 0, st, (void*)(base + o_tot), nblocks);
-    ZK_CHECK_LAUNCH();
-    // chaining: P_s = prod_{j < n - bf - 1} frac_s[j] = local[src] * block_prefix[src / span], src = n - bf - 2
-    const uint32_t src = n - bf - 2;
-    std::vector<u256> loc(n_sets), pre(n_sets), inits(n_sets);
-    for (size_t sidx = 0; sidx < n_sets; sidx++) {
-        ZK_HIP(hipMemcpyAsync(&loc[sidx], base + o_num + (sidx * (size_t)n + src) * 32, 32, hipMemcpyDeviceToHost, st));
-        ZK_HIP(hipMemcpyAsync(&pre[sidx], base + o_tot + (sidx * (size_t)nblocks + src / span) * 32, 32, hipMemcpyDeviceToHost, st));
-    }
-    ZK_HIP(hipStreamSynchronize(st));
-    u256 init = Fr::one();
-    for (size_t sidx = 0; sidx < n_sets; sidx++) { inits[sidx] = init; init = Fr::mul(init, Fr::mul(loc[sidx], pre[sidx])); }
-    ZK_HIP(hipMemcpyAsync(base + o_in, inits.data(), n_sets * 32, hipMemcpyHostToDevice, st));
-    ZK_LAUNCH(gp_assemble_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)n_sets), blk, 0, st, (const void*)(base + o_num), (const void*)(base + o_tot), n, n - bf,
-              (const void*)(base + o_in), (const void*)(base + o_bl), bf, (void* const*)(base + o_zp), nblocks);
-    ZK_CHECK_LAUNCH();
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    if (bf + 1 >= n) return ctx->fail(ZK_ERR_ARG, "zk_lookup_product_dev: blinding_factors too large");
+    const void* cols4[4] = {cin, ctab, pin, ptab};
+    return lookup_product_batch(ctx, cols4, 1, k, beta, gamma, blinding, bf, &d_z);
 }
 
 }  // namespace zk

@@ -7,140 +7,31 @@
 //        multiset; a value missing from the table is a ConstraintSystemFailure); the remaining ("repeated") rows are
 //        filled with the leftover table values in ascending order, handed out from the LAST repeated row backwards
 //        (the CPU code pops a Vec);  both columns end with blinding_factors + 1 caller-supplied random rows.
-// The CPU version is a sort + BTreeMap walk.  Here: LSD radix sort of row indices on 4-bit digits of the canonical
-// 256-bit keys (stable, per-thread runs + one scan per digit, digits on which all keys agree are skipped), a
-// lower_bound per distinct value to take its table copy, two prefix sums to rank repeated rows and leftover values,
-// and one gather to assemble both columns.
+// The CPU version is a sort + BTreeMap walk.  Here all lookups of a proof go through one call (zk_lookup_permute_dev is a batch of one):
+//   1. every input column and every distinct table column is sorted by a stable LSD radix sort of (64-bit key, row index) pairs on 8-bit
+//      digits, the key being the 64-bit window of the canonical value that ends at the highest bit any key of that column uses;
+//   2. where the window does not cover the keys, an order check against the full 256-bit order finds the columns whose rows tie on the
+//      window but differ below it; the bits those rows differ in are collected (tie mask) and the column is sorted again, stably, over
+//      that bit range and then over the window: exact (see lpb_tiemask_kernel).  A context remembers such columns per call shape and
+//      sorts them in those two stages straight away (the order check still guards them);
+//   3. a lower_bound per distinct value takes its table copy, two prefix sums rank repeated rows and leftover values, and one gather
+//      assembles both columns.
+// 
 #include "ctx.h"
 #include <vector>
 
 namespace zk {
 
-constexpr uint32_t LP_RUN = 64;     // consecutive items ranked by one thread (stability)
-constexpr uint32_t LP_T = 256;
-
-// canonical keys + identity permutation; ormask[0..8) collects the OR of all keys so that the sort only visits the
-// digits some key actually uses (witness values are mostly far below 254 bits)
-ZK_KERNEL void lp_canon_kernel(const void* x, uint32_t u, void* canon, uint32_t* idx, uint32_t* ormask) {
-    __shared__ uint32_t lor[8];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (threadIdx.x < 8) lor[threadIdx.x] = 0;
-    __syncthreads();
-    if (i < u) {
-        const u256 c = Fr::from_mont(load_u256(x, i));
-        store_u256(canon, i, c);
-        idx[i] = i;
-#pragma unroll
-        for (int w = 0; w < 8; w++) if (c.v[w] & ~lor[w]) atomicOr(&lor[w], c.v[w]);   // workgroup-local first: the global words are hit once per workgroup
-    }
-    __syncthreads();
-    if (threadIdx.x < 8 && lor[threadIdx.x]) atomicOr(&ormask[threadIdx.x], lor[threadIdx.x]);
-}
-ZK_HD uint32_t lp_digit(const void* canon, uint32_t row, uint32_t d) {  // d-th 4-bit digit, d = 0 least significant
-    const uint32_t w = reinterpret_cast<const uint32_t*>(canon)[(size_t)row * 8 + (d >> 3)];
-    return (w >> (4 * (d & 7))) & 15u;
-}
-// counts[bin * nthreads + t] = how many items of run t carry digit `bin`
-ZK_KERNEL void lp_hist_kernel(const void* canon, const uint32_t* idx, uint32_t u, uint32_t d, uint32_t nruns, uint32_t* counts) {
-    __shared__ uint32_t lc[16 * LP_T];
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, tid = threadIdx.x;
-    for (uint32_t b = 0; b < 16; b++) lc[b * LP_T + tid] = 0;
-    if (t < nruns) {
-        const uint32_t lo = t * LP_RUN, hi = lo + LP_RUN < u ? lo + LP_RUN : u;
-        for (uint32_t i = lo; i < hi; i++) lc[lp_digit(canon, idx[i], d) * LP_T + tid]++;
-        for (uint32_t b = 0; b < 16; b++) counts[(size_t)b * nruns + t] = lc[b * LP_T + tid];
-    }
-}
-// single workgroup: exclusive scan of v[0..m) in place; *total_out = sum; flag[0] = 1 if some bin holds every item (digit pass is a no-op)
-ZK_KERNEL void lp_scan_kernel(uint32_t* v, uint32_t m, uint32_t nruns, uint32_t u, uint32_t* flag, uint32_t* total_out) {
-    __shared__ uint32_t part[1024];
-    const uint32_t T = blockDim.x, tid = threadIdx.x;
-    const uint32_t per = (m + T - 1) / T;
-    const uint32_t lo = tid * per < m ? tid * per : m, hi = lo + per < m ? lo + per : m;
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; i++) s += v[i];
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < T; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - s;
-    for (uint32_t i = lo; i < hi; i++) { const uint32_t x = v[i]; v[i] = run; run += x; }
-    __syncthreads();
-    if (tid == 0) {
-        if (total_out) *total_out = part[T - 1];
-        if (flag && nruns) {
-            uint32_t skip = 0;
-            for (uint32_t b = 0; b < 16; b++) {
-                const uint32_t start = v[(size_t)b * nruns];
-                const uint32_t end = b == 15 ? part[T - 1] : v[(size_t)(b + 1) * nruns];
-                if (end - start == u) skip = 1;
-            }
-            flag[0] = skip;
-        }
-    }
-}
-ZK_KERNEL void lp_scatter_kernel(const void* canon, const uint32_t* idx_in, uint32_t* idx_out, uint32_t u, uint32_t d, uint32_t nruns,
-                                 const uint32_t* offsets, const uint32_t* flag) {
-    __shared__ uint32_t lo_[16 * LP_T];
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, tid = threadIdx.x;
-    if (t >= nruns) return;
-    const uint32_t lo = t * LP_RUN, hi = lo + LP_RUN < u ? lo + LP_RUN : u;
-    if (flag[0]) { for (uint32_t i = lo; i < hi; i++) idx_out[i] = idx_in[i]; return; }
-    for (uint32_t b = 0; b < 16; b++) lo_[b * LP_T + tid] = offsets[(size_t)b * nruns + t];
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t r = idx_in[i];
-        idx_out[lo_[lp_digit(canon, r, d) * LP_T + tid]++] = r;
-    }
-}
-
-
-// ---- fast path: stable LSD radix sort of (64-bit key, row index) pairs, 8-bit digits -----------------------------
-// The sort key is the 64-bit window of the canonical value that ends at the highest bit any key of the pair of columns
-// uses (theta-compressed expressions are full-width, range-check inputs are a few bits wide).  When that window does
-// not cover a key completely the result is checked against the full 256-bit order afterwards and the generic 4-bit
-// path above is taken if two rows tie on the window but differ below it (for random values: never in practice).
-// Per pass: one histogram launch and one scatter launch.  A workgroup owns a tile of FS_T * FS_E consecutive pairs;
+// ---- stable LSD radix sort of (64-bit key, row index) pairs, 8-bit digits ----------------------------------------------
+// Per pass: one histogram launch, one offsets launch and one scatter launch.  A workgroup owns a tile of FS_T * FS_E consecutive pairs;
 // stability inside the tile comes from per-thread runs ranked through an LDS count matrix [thread][digit], stability
 // across tiles from the workgroup-major global histogram (each workgroup sums the rows of the workgroups before it).
 constexpr uint32_t FS_T = 256, FS_E = 16, FS_TILE = FS_T * FS_E, FS_PAD = 258;
 
 ZK_HD uint32_t fs_digit(uint2 k, uint32_t pass) { return ((pass < 4 ? k.x : k.y) >> (8 * (pass & 3))) & 255u; }
 
-// ---- exclusive scan of u32 flags over many workgroups (ranks of repeated rows / leftover table values) ----------------
+// exclusive scans of u32 flags over many workgroups (ranks of repeated rows / leftover table values): tiles of XS_T * XS_E
 constexpr uint32_t XS_T = 256, XS_E = 8, XS_TILE = XS_T * XS_E;
-ZK_KERNEL void xs_tile_sum_kernel(const uint32_t* v, uint32_t m, uint32_t* sums) {
-    __shared__ uint32_t part[XS_T];
-    const uint32_t tid = threadIdx.x, base = blockIdx.x * XS_TILE;
-    uint32_t s = 0;
-    for (uint32_t e = 0; e < XS_E; e++) { const uint32_t i = base + e * XS_T + tid; if (i < m) s += v[i]; }
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = XS_T >> 1; d > 0; d >>= 1) { if (tid < d) part[tid] += part[tid + d]; __syncthreads(); }
-    if (tid == 0) sums[blockIdx.x] = part[0];
-}
-// in place: v[i] <- exclusive prefix; sums[] must already hold the EXCLUSIVE scan of the tile sums
-ZK_KERNEL void xs_apply_kernel(uint32_t* v, uint32_t m, const uint32_t* sums) {
-    __shared__ uint32_t part[XS_T];
-    const uint32_t tid = threadIdx.x, lo = blockIdx.x * XS_TILE + tid * XS_E;
-    uint32_t x[XS_E], s = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < XS_E; e++) { x[e] = lo + e < m ? v[lo + e] : 0u; s += x[e]; }
-    part[tid] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < XS_T; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = sums[blockIdx.x] + part[tid] - s;
-#pragma unroll
-    for (uint32_t e = 0; e < XS_E; e++) { if (lo + e < m) v[lo + e] = run; run += x[e]; }
-}
 
 ZK_HD int lp_cmp(const u256& a, const u256& b) {  // numeric compare of canonical values
     for (int i = 7; i >= 0; i--) {
@@ -149,168 +40,15 @@ ZK_HD int lp_cmp(const u256& a, const u256& b) {  // numeric compare of canonica
     }
     return 0;
 }
-// first[i] = 1 iff sorted input row i starts a new value; such a row takes one copy of its value out of the table
-ZK_KERNEL void lp_mark_kernel(const void* in_canon, const uint32_t* in_idx, const void* tab_canon, const uint32_t* tab_idx, uint32_t u,
-                              uint32_t* repeated, uint32_t* unconsumed, uint32_t* err) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= u) return;
-    const u256 v = load_u256(in_canon, in_idx[i]);
-    const bool first = i == 0 || lp_cmp(v, load_u256(in_canon, in_idx[i - 1])) != 0;
-    repeated[i] = first ? 0u : 1u;
-    if (!first) return;
-    uint32_t lo = 0, hi = u;      // lower_bound in the sorted table
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (lp_cmp(load_u256(tab_canon, tab_idx[mid]), v) < 0) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= u || lp_cmp(load_u256(tab_canon, tab_idx[lo]), v) != 0) { atomicAdd(err, 1u); return; }
-    unconsumed[lo] = 0;           // distinct values hit distinct table slots
-}
-ZK_KERNEL void lp_fill_kernel(uint32_t* a, uint32_t n, uint32_t val) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = val;
-}
-// leftover[rank] = sorted-table position of the rank-th unconsumed table entry
-ZK_KERNEL void lp_compact_kernel(const uint32_t* unconsumed_flag, const uint32_t* rank, uint32_t u, uint32_t* leftover) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < u && unconsumed_flag[t]) leftover[rank[t]] = t;
-}
-ZK_KERNEL void lp_assemble_kernel(const void* in_mont, const uint32_t* in_idx, const void* tab_mont, const uint32_t* tab_idx, const uint32_t* repeated_flag,
-                                  const uint32_t* rep_rank, const uint32_t* leftover, uint32_t n_rep, uint32_t u, uint32_t n, const void* blind_in,
-                                  const void* blind_tab, void* out_in, void* out_tab) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (i >= u) {
-        store_u256(out_in, i, load_u256(blind_in, i - u));
-        store_u256(out_tab, i, load_u256(blind_tab, i - u));
-        return;
-    }
-    const u256 v = load_u256(in_mont, in_idx[i]);
-    store_u256(out_in, i, v);
-    if (!repeated_flag[i]) store_u256(out_tab, i, v);
-    else store_u256(out_tab, i, load_u256(tab_mont, tab_idx[leftover[n_rep - 1 - rep_rank[i]]]));   // last repeated row gets the smallest leftover
-}
-
-// ---- host ------------------------------------------------------------------------------------------
-// sorts `idx` (0..u) by the canonical keys; returns the buffer that holds the result
 static uint32_t lp_scan_threads(uint32_t m) {   // single-workgroup scan: enough threads for ~8 items each, power of two
     uint32_t t = 64;
     while (t < 1024 && t * 8 < m) t <<= 1;
     return t;
 }
-static int lp_sort(zk_ctx* ctx, const void* canon, uint32_t u, uint32_t ndigits, uint32_t* idx_a, uint32_t* idx_b, uint32_t* counts, uint32_t* flag, uint32_t** result) {
-    const uint32_t nruns = (u + LP_RUN - 1) / LP_RUN;
-    const uint32_t grid = (nruns + LP_T - 1) / LP_T;
-    uint32_t* in = idx_a;
-    uint32_t* out = idx_b;
-    for (uint32_t d = 0; d < ndigits; d++) {
-        ZK_LAUNCH(lp_hist_kernel, grid, LP_T, 0, ctx->stream, canon, (const uint32_t*)in, u, d, nruns, counts);
-        ZK_CHECK_LAUNCH();
-        ZK_LAUNCH(lp_scan_kernel, 1, lp_scan_threads(16 * nruns), 0, ctx->stream, counts, 16 * nruns, nruns, u, flag, (uint32_t*)nullptr);
-        ZK_CHECK_LAUNCH();
-        ZK_LAUNCH(lp_scatter_kernel, grid, LP_T, 0, ctx->stream, canon, (const uint32_t*)in, out, u, d, nruns, (const uint32_t*)counts, (const uint32_t*)flag);
-        ZK_CHECK_LAUNCH();
-        std::swap(in, out);
-    }
-    *result = in;
-    return ZK_OK;
-}
-
-
-// v[0..m) <- exclusive scan, *total_dev <- sum (sums: scratch of ceil(m / XS_TILE) + 1 words)
-static int xs_scan(zk_ctx* ctx, uint32_t* v, uint32_t m, uint32_t* sums, uint32_t* total_dev) {
-    hipStream_t st = ctx->stream;
-    const uint32_t nt = (m + XS_TILE - 1) / XS_TILE;
-    ZK_LAUNCH(xs_tile_sum_kernel, nt, XS_T, 0, st, (const uint32_t*)v, m, sums);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(lp_scan_kernel, 1, lp_scan_threads(nt), 0, st, sums, nt, 0u, m, (uint32_t*)nullptr, total_dev);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(xs_apply_kernel, nt, XS_T, 0, st, v, m, (const uint32_t*)sums);
-    ZK_CHECK_LAUNCH();
-    return ZK_OK;
-}
-
-// One lookup on the every-digit path (4-bit digits over all bits in use): the fallback of the batched form below for a lookup whose keys tie on the
-// 64-bit window but differ below it.
-static int lookup_permute_one(zk_ctx* ctx, const void* d_input, const void* d_table, uint32_t k, uint32_t blinding_factors, const void* h_blind_input,
-                              const void* h_blind_table, void* d_out_input, void* d_out_table) {
-    if (!d_input || !d_table || !d_out_input || !d_out_table || !h_blind_input || !h_blind_table)
-        return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: null argument");
-    if (k < 1 || k > 26) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: k = %u out of range", k);
-    const uint32_t n = 1u << k, nb = blinding_factors + 1;
-    if (nb >= n) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: blinding_factors too large");
-    const uint32_t u = n - nb;
-    const uint32_t nruns = (u + LP_RUN - 1) / LP_RUN;
-    const uint32_t nxs = (u + XS_TILE - 1) / XS_TILE + 1;
-    // workspace: canon_in | canon_tab | blind (2*nb) | u32 arrays
-    const size_t words = (size_t)4 * u /*idx in a/b, tab a/b*/ + (size_t)16 * nruns + 4 * (size_t)u /*repeated, rep_rank, unconsumed, left_rank*/ + u + nxs + 64;
-    ZK_HIP(ctx->ws_tmp.ensure((size_t)u * 64 + (size_t)nb * 64 + words * 4 + 512));
-    char* base = (char*)ctx->ws_tmp.p;
-    void* canon_in = base;
-    void* canon_tab = base + (size_t)u * 32;
-    void* d_blind_in = base + (size_t)u * 64;
-    void* d_blind_tab = (char*)d_blind_in + (size_t)nb * 32;
-    uint32_t* w = (uint32_t*)((char*)d_blind_tab + (size_t)nb * 32);
-    uint32_t* in_a = w; uint32_t* in_b = in_a + u; uint32_t* tab_a = in_b + u; uint32_t* tab_b = tab_a + u;
-    uint32_t* counts = tab_b + u;
-    uint32_t* repeated = counts + (size_t)16 * nruns; uint32_t* rep_rank = repeated + u;
-    uint32_t* unconsumed = rep_rank + u; uint32_t* left_rank = unconsumed + u;
-    uint32_t* leftover = left_rank + u;
-    uint32_t* xsums = leftover + u;
-    uint32_t* scal = xsums + nxs;       // [0] skip flag, [1] error count, [2] n_rep, [3] n_left, [4..12) OR of all keys
-    hipStream_t st = ctx->stream;
-    const int blk = ctx->tune.vec_block;
-    const uint32_t g = (u + blk - 1) / blk;
-    ZK_HIP(hipMemsetAsync(scal, 0, 64, st));
-    ZK_HIP(hipMemcpyAsync(d_blind_in, h_blind_input, (size_t)nb * 32, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(d_blind_tab, h_blind_table, (size_t)nb * 32, hipMemcpyHostToDevice, st));
-    ZK_LAUNCH(lp_canon_kernel, g, blk, 0, st, d_input, u, canon_in, in_a, scal + 4);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(lp_canon_kernel, g, blk, 0, st, d_table, u, canon_tab, tab_a, scal + 4);
-    ZK_CHECK_LAUNCH();
-    uint32_t om[8];
-    ZK_HIP(hipMemcpyAsync(om, scal + 4, 32, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    uint32_t nbits = 1;                                     // number of bits any key of either column uses
-    for (int wd = 7; wd >= 0; wd--)
-        if (om[wd]) { uint32_t top = 31; while (!((om[wd] >> top) & 1)) top--; nbits = (uint32_t)wd * 32 + top + 1; break; }
-    const uint32_t ndigits = (nbits + 3) / 4;
-    uint32_t *in_sorted = nullptr, *tab_sorted = nullptr;
-    int rc = lp_sort(ctx, canon_in, u, ndigits, in_a, in_b, counts, scal, &in_sorted);
-    if (rc) return rc;
-    rc = lp_sort(ctx, canon_tab, u, ndigits, tab_a, tab_b, counts, scal, &tab_sorted);
-    if (rc) return rc;
-    ZK_LAUNCH(lp_fill_kernel, g, blk, 0, st, unconsumed, u, 1u);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(lp_mark_kernel, g, blk, 0, st, (const void*)canon_in, (const uint32_t*)in_sorted, (const void*)canon_tab, (const uint32_t*)tab_sorted, u, repeated,
-              unconsumed, scal + 1);
-    ZK_CHECK_LAUNCH();
-    ZK_HIP(hipMemcpyAsync(rep_rank, repeated, (size_t)u * 4, hipMemcpyDeviceToDevice, st));
-    ZK_HIP(hipMemcpyAsync(left_rank, unconsumed, (size_t)u * 4, hipMemcpyDeviceToDevice, st));
-    rc = xs_scan(ctx, rep_rank, u, xsums, scal + 2);
-    if (rc) return rc;
-    rc = xs_scan(ctx, left_rank, u, xsums, scal + 3);
-    if (rc) return rc;
-    uint32_t hs[4];
-    ZK_HIP(hipMemcpyAsync(hs, scal, 16, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    if (hs[1]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: %u input value(s) are not in the table (halo2: Error::ConstraintSystemFailure)", hs[1]);
-    if (hs[2] != hs[3]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: internal count mismatch (%u repeated rows, %u leftover table values)", hs[2], hs[3]);
-    ZK_LAUNCH(lp_compact_kernel, g, blk, 0, st, (const uint32_t*)unconsumed, (const uint32_t*)left_rank, u, leftover);
-    ZK_CHECK_LAUNCH();
-    ZK_LAUNCH(lp_assemble_kernel, (n + blk - 1) / blk, blk, 0, st, d_input, (const uint32_t*)in_sorted, d_table, (const uint32_t*)tab_sorted,
-              (const uint32_t*)repeated, (const uint32_t*)rep_rank, (const uint32_t*)leftover, hs[2], u, n, (const void*)d_blind_in, (const void*)d_blind_tab,
-              d_out_input, d_out_table);
-    ZK_CHECK_LAUNCH();
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
-}
-
 
 // ================================================================================================================
-// batched form: all lookup arguments of a proof in one call.  Every kernel below is the single-lookup kernel with
-// blockIdx.y selecting the sort (s = 2 * lookup + {0 input, 1 table}) or the lookup, so a proof pays 2 launches per
-// radix pass instead of 2 per pass per column, and the grids are large enough to fill the chip.
+// All lookup arguments of a proof in one call: blockIdx.y selects the sorted column, the sort (s = 2 * lookup + {0 input, 1 table})
+// or the lookup, so a proof pays the launches of a radix pass once, not once per column, and the grids are large enough to fill the chip.
 // Layout (S = 2 * count sorts, u rows each): canon[s][u] | keys a/b [s][u] | idx a/b [s][u] | flags[s][u] (repeated / unconsumed)
 // | ranks[s][u] | leftover[l][u] | ghist[s][nwg][256] | xsums[s][nxs] | scal[l][16]
 // ================================================================================================================
@@ -473,7 +211,7 @@ ZK_KERNEL void lpb_check_kernel(LpbArgs a, const uint32_t* idx_sorted) {
 // Columns whose rows tie on the 64-bit window but differ below it (theta-compressed lookups whose LAST expression differs: v and v + small —
 // the base64 lookups of the sgx circuit do, their last expression is a 2-bit chunk): cscal[s][0..8) <- OR over adjacent window-tied rows of x ^ y.
 // Any two tied values differ only inside that mask (x ^ z is the XOR of the adjacent XORs between them), so a stable LSD sort over the mask's
-// bit range followed by the window passes orders the column exactly — a few extra passes instead of the every-digit sort.
+// bit range followed by the window passes orders the column exactly (the mask lies below the window's shift).
 ZK_KERNEL void lpb_tiemask_kernel(LpbArgs a, const uint32_t* idx_sorted) {
     __shared__ uint32_t lor[8];
     const uint32_t s = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -786,7 +524,7 @@ int lookup_permute_batch(zk_ctx* ctx, const void* const* d_inputs, const void* c
     std::vector<uint32_t>& hint = ctx->lookup_tie_hint[hint_key];         // per column: 0 = none, else 1 + highest differing bit seen
     if (hint.size() != C) hint.assign(C, 0);
     std::vector<uint32_t> plain, hinted;
-    for (uint32_t c = 0; c < C; c++) (hint[c] && shifts[c] && !ctx->tune.lookup_force_generic_sort ? hinted : plain).push_back(c);
+    for (uint32_t c = 0; c < C; c++) (hint[c] && shifts[c] ? hinted : plain).push_back(c);
     {
         std::vector<std::vector<uint32_t>> ss(1, std::vector<uint32_t>(plain.size()));
         for (size_t f = 0; f < plain.size(); f++) ss[0][f] = shifts[plain[f]];
@@ -808,7 +546,7 @@ int lookup_permute_batch(zk_ctx* ctx, const void* const* d_inputs, const void* c
         ZK_HIP(hipStreamSynchronize(st));
         std::vector<uint32_t> fcols;
         for (uint32_t c = 0; c < C; c++) if (csc[(size_t)c * 16 + 8]) fcols.push_back(c);
-        if (!fcols.empty() && !ctx->tune.lookup_force_generic_sort) {
+        if (!fcols.empty()) {
             // window ties (first seen, or a hinted column whose ties reached above the hinted range): which bits do tied rows differ in?
             std::vector<uint32_t> lo_bit, hi_bit;
             int rc = tie_ranges(fcols, lo_bit, hi_bit);
@@ -839,10 +577,11 @@ int lookup_permute_batch(zk_ctx* ctx, const void* const* d_inputs, const void* c
     ZK_HIP(hipMemcpyAsync(sc.data(), a.scal, count * 64, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipMemcpyAsync(csc.data(), a.cscal, (size_t)C * 64, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
-    std::vector<size_t> redo;
     for (size_t l = 0; l < count; l++) {
         const uint32_t* h = &sc[l * 16];
-        if (csc[l * 16 + 8] || csc[(size_t)tabcol[l] * 16 + 8] || ctx->tune.lookup_force_generic_sort) { redo.push_back(l); continue; }   // window ties: every-digit sort for this lookup
+        if (csc[l * 16 + 8] || csc[(size_t)tabcol[l] * 16 + 8])      // the refinement sorts exactly: a violation left is a bug
+            return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: internal order violation in lookup %zu (%u input / %u table row pairs out of order after refinement)", l,
+                             csc[l * 16 + 8], csc[(size_t)tabcol[l] * 16 + 8]);
         if (h[1]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: %u input value(s) of lookup %zu are not in the table (halo2: Error::ConstraintSystemFailure)", h[1], l);
         if (h[2] != h[3]) return ctx->fail(ZK_ERR_ARG, "zk_lookup_permute_dev: internal count mismatch in lookup %zu (%u repeated rows, %u leftover table values)", l, h[2], h[3]);
     }
@@ -851,13 +590,7 @@ int lookup_permute_batch(zk_ctx* ctx, const void* const* d_inputs, const void* c
     ZK_LAUNCH(lpb_assemble_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, st, a, sorted);
     ZK_CHECK_LAUNCH();
     ZK_HIP(hipStreamSynchronize(st));
-    ctx->last_ms["lookup_sorts"] += (double)count;                     // statistics (zk_timing_get): lookups sorted, and how many took the every-digit path
-    ctx->last_ms["lookup_generic_sorts"] += (double)redo.size();
-    for (size_t l : redo) {
-        int rc = lookup_permute_one(ctx, d_inputs[l], d_tables[l], k, blinding_factors, (const char*)h_blind_inputs + l * (size_t)nb * 32,
-                                    (const char*)h_blind_tables + l * (size_t)nb * 32, d_out_inputs[l], d_out_tables[l]);
-        if (rc) return rc;
-    }
+    ctx->last_ms["lookup_sorts"] += (double)count;                     // statistics (zk_timing_get): lookups sorted
     return ZK_OK;
 }
 int lookup_permute(zk_ctx* ctx, const void* d_input, const void* d_table, uint32_t k, uint32_t blinding_factors, const void* h_blind_input,
