@@ -297,6 +297,12 @@ int zk_quotient_program_part_opmix(zk_ctx* ctx, uint64_t prog, uint32_t part, ui
 int zk_quotient_run_high_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args);
 int zk_quotient_run_low_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t low_cosets);
 int zk_quotient_run_coset_part_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part);
+/* halo2's fold across the circuits of one proof (evaluate_h does not reset `values` between circuits: circuit c's Horner starts from circuit c-1's result).
+ * As zk_quotient_run_dev / _coset_dev / _coset_part_dev, but args->out holds the previous value on entry:
+ * out <- out * y^E + numerator, E = the identities of the WHOLE program (gate polynomials, 2 + (n_sets - 1) + n_sets of the permutation, 5 per lookup), also for a degree part
+ * (so high + low still sum to the whole).  coset = UINT32_MAX: the whole extended domain; part 0 = whole program, 1 = high, 2 = low (low: low_cosets from the program).
+ * The fold is inside the launch: its only extra traffic is one read of out. */
+int zk_quotient_run_acc_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part);
 int zk_coeff_to_coset_batch_dev(zk_ctx* ctx, const void* const* coeffs_dev, void* const* outs_dev, size_t count, uint32_t k, uint32_t extended_k, uint32_t coset);
 int zk_fr_interleave_dev(zk_ctx* ctx, const void* const* cosets_dev, size_t count, size_t n, void* out_dev);   /* out[i * count + j] = cosets[j][i] */
 /* The pieces of h(X) straight from the numerator's values on cosets 0 .. pieces-1 (vanishing::Argument::construct: divide_by_vanishing_poly + extended_to_coeff + the split
@@ -326,7 +332,7 @@ int zk_evaluate_h(zk_ctx* ctx, uint64_t pk, const void* const* advice_polys, con
 
 /* ---- the whole per-proof path: replaces plonk::create_proof + ProverSHPLONK ------------------------------------- *
  * halo2_proofs src/plonk/prover.rs create_proof::<KZGCommitmentScheme<Bn256>, ProverSHPLONK, Challenge255, _, Blake2bWrite, _> as the reference calls it
- * (circuits/src/sgx_dcap_verifier.rs:814-822), single circuit instance, no user challenges: every O(n) step runs through the entry points above in the
+ * (circuits/src/sgx_dcap_verifier.rs:814-822), one or several circuit instances (zk_plonk_create_proof_multi), no user challenges: every O(n) step runs through the entry points above in the
  * order of INTEGRATION.md's phase table, columns stay in HBM from the advice commitment to the last SHPLONK commitment, Fiat-Shamir hashing (Blake2b,
  * Challenge255), point encoding (y parity in bit 255) and the rotation-set bookkeeping run on the host inside this call.  This is the native (C++) form of
  * the phase-batched prover; zk-dcap-verifier_amd/plonk/prover.py is its Python twin and both emit the same bytes for the same inputs and draws.
@@ -444,8 +450,18 @@ int zk_plonk_pk_release(zk_ctx* ctx, uint64_t pk);
 int zk_plonk_pk_descriptor(zk_ctx* ctx, uint64_t pk, const zk_plonk_pk_desc** desc);
 int zk_plonk_prove(zk_ctx* ctx, uint64_t pk, const void* const* advice, int advice_on_device, const void* const* instances, const uint32_t* instance_lens,
                    zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len);
+/* halo2's create_proof over a slice of circuits (create_proof(params, pk, &[c0, c1, ..], &[inst0, inst1, ..], ..)): ONE proof over n_circuits circuits sharing the key —
+ * one vanishing argument, one set of fixed and sigma evaluations, one SHPLONK opening, one pairing check for the verifier.  Transcript and draws follow halo2 circuit by
+ * circuit wherever halo2 loops over the circuits ("Several circuits in one proof"); every phase is one batched launch over the columns of all circuits.
+ * advice = n_circuits x n_advice pointers, circuit-major; instances / instance_lens = n_circuits x n_instance, circuit-major.  n_circuits = 1: byte for byte
+ * zk_plonk_create_proof.  n_circuits = 0, or > 1 on a sharded descriptor (shard_world > 1): ZK_ERR_ARG. */
+int zk_plonk_create_proof_multi(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t n_circuits, const void* const* advice, int advice_on_device,
+                                const void* const* instances, const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user,
+                                void* proof_out, size_t proof_cap, size_t* proof_len);
+int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
+                         const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len);
 /* wall milliseconds of the nine phases (instances, advice, lookups, grand products, random poly, h numerator, h commit, evaluations, SHPLONK) of the
- * calling thread's last zk_plonk_create_proof */
+ * calling thread's last zk_plonk_create_proof / zk_plonk_create_proof_multi (a phase of an m-circuit proof covers all m circuits) */
 int zk_plonk_last_phase_ms(double out[9]);
 /* return the per-proof device buffers zk_plonk_create_proof keeps for reuse on this context (zk_ctx_destroy does it too) */
 int zk_plonk_trim(zk_ctx* ctx);

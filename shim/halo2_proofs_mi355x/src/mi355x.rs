@@ -43,6 +43,26 @@ pub struct ZkQuotientArgs {
     pub out: *mut c_void,
 }
 
+/// zk_plonk_pk_desc: opaque on this side (the library's own key fills it: zk_plonk_pk_build / zk_plonk_pk_descriptor; this shim proves through key handles)
+#[repr(C)]
+#[derive(Debug)]
+pub struct ZkPlonkPkDesc { _opaque: [u8; 0] }
+/// zk_rng_fn: the caller's `Fr::random` (create_proof_native.rs: `draw`)
+pub type ZkRngFn = extern "C" fn(user: *mut c_void, n: usize, out_fr: *mut c_void);
+
+extern "C" {
+    /// one proof over several circuits (halo2's `&[c0, c1, ..]`): advice = n_circuits x n_advice, instances / instance_lens = n_circuits x n_instance, circuit-major
+    pub fn zk_plonk_create_proof_multi(ctx: *mut ZkCtx, pk: *const ZkPlonkPkDesc, n_circuits: u32, advice: *const *const c_void, advice_on_device: c_int,
+                                       instances: *const *const c_void, instance_lens: *const u32, rng: ZkRngFn, rng_user: *mut c_void,
+                                       proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn zk_plonk_prove(ctx: *mut ZkCtx, pk: u64, advice: *const *const c_void, advice_on_device: c_int, instances: *const *const c_void,
+                          instance_lens: *const u32, rng: ZkRngFn, rng_user: *mut c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    pub fn zk_plonk_prove_multi(ctx: *mut ZkCtx, pk: u64, n_circuits: u32, advice: *const *const c_void, advice_on_device: c_int, instances: *const *const c_void,
+                                instance_lens: *const u32, rng: ZkRngFn, rng_user: *mut c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    /// halo2's fold across circuits: out <- out * y^E + numerator (coset = u32::MAX: the whole extended domain; part 0 whole, 1 high, 2 low)
+    pub fn zk_quotient_run_acc_dev(ctx: *mut ZkCtx, prog: u64, args: *const ZkQuotientArgs, coset: u32, part: u32) -> c_int;
+}
+
 extern "C" {
     fn zk_abi_version() -> u32;
     fn zk_abi_struct_size(struct_name: *const c_char) -> u32;

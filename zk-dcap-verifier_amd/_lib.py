@@ -509,9 +509,10 @@ class Backend:
 
     def quotient_run_dev(self, prog: int, *, fixed, advice, instance, l0, l_last, l_active_row, perm_cosets, perm_products,
                          lookup_product, lookup_input, lookup_table, challenges, beta, gamma, theta, y, out, coset: int | None = None,
-                         rows: tuple | None = None, part: int = 0, low_cosets: int = 0):
+                         rows: tuple | None = None, part: int = 0, low_cosets: int = 0, accumulate: bool = False):
         """part 1 / 2: the high / low part of a program with a degree split (zk_quotient_run_high_dev / _low_dev / _coset_part_dev); low_cosets: the low part on the rows of
-        that many cosets of extended-layout columns, `out` coset-major"""
+        that many cosets of extended-layout columns, `out` coset-major.  accumulate: `out` holds the previous value, out <- out * y^E + numerator (zk_quotient_run_acc_dev;
+        the low part on the whole domain then runs on the program's own low cosets)"""
         keep = []
 
         def parr(cols):
@@ -525,7 +526,10 @@ class Backend:
                          parr(perm_cosets), parr(perm_products), len(perm_products),
                          parr(lookup_product), parr(lookup_input), parr(lookup_table),
                          ch.ctypes.data, sc[0].ctypes.data, sc[1].ctypes.data, sc[2].ctypes.data, sc[3].ctypes.data, _dptr(out))
-        if part:
+        if accumulate:
+            assert rows is None
+            self._ck(self.lib.zk_quotient_run_acc_dev(self.ctx, C.c_uint64(prog), C.byref(a), C.c_uint32(0xFFFFFFFF if coset is None else coset), C.c_uint32(part)))
+        elif part:
             assert rows is None
             if coset is not None:
                 self._ck(self.lib.zk_quotient_run_coset_part_dev(self.ctx, C.c_uint64(prog), C.byref(a), C.c_uint32(coset), C.c_uint32(part)))

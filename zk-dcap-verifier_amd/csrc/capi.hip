@@ -23,6 +23,8 @@ int lookup_product(zk_ctx* ctx, const void* cin, const void* ctab, const void* p
                    const void* blinding, uint32_t bf, void* d_z);
 int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
                             const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs);
+int permutation_product_circuits(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, size_t n_circuits, uint32_t chunk_len, uint32_t k,
+                                 const void* beta, const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs);
 int lookup_product_batch(zk_ctx* ctx, const void* const* cols4, size_t count, uint32_t k, const void* beta, const void* gamma, const void* blinding,
                          uint32_t bf, void* const* d_zs);
 int eval_polynomial_batch(zk_ctx* ctx, const void* const* polys, size_t count, size_t n, const void* points, void* out);
@@ -47,7 +49,7 @@ int quotient_program_release(zk_ctx* ctx, uint64_t prog);
 int quotient_program_info(zk_ctx* ctx, uint64_t prog, uint32_t* n_instr, uint32_t* n_slots, uint32_t* n_columns);
 int quotient_program_kernels(zk_ctx* ctx, uint64_t prog, uint32_t* n_kernels);
 int quotient_program_opmix(zk_ctx* ctx, uint64_t prog, uint32_t part, uint32_t counts[9]);
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets);
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate);
 int quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low);
 int domain_coeff_to_coset_batch(zk_ctx* ctx, const void* const* coeffs, void* const* outs, size_t count, uint32_t k, uint32_t ek, uint32_t coset);
 int fr_interleave(zk_ctx* ctx, const void* const* h_cosets, size_t count, size_t n, void* d_out);
@@ -483,6 +485,13 @@ int zk_permutation_product_all_dev(zk_ctx* ctx, const void* const* values, const
                                    const void* beta, const void* gamma, const void* blinding, uint32_t blinding_factors, void* const* z_devs) ZK_ABI_TRY {
     ENTER; return permutation_product_all(ctx, values, sigmas, n_columns, chunk_len, k, beta, gamma, blinding, blinding_factors, z_devs);
 } ZK_ABI_CATCH(ctx)
+}  // extern "C"
+// prover.hip (an m-circuit proof): the permutation arguments of all circuits in one launch sequence (zk_permutation_product_all_dev per circuit, batched)
+int zk_internal_permutation_products(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t n_columns, size_t n_circuits, uint32_t chunk_len, uint32_t k,
+                                     const void* beta, const void* gamma, const void* blinding, uint32_t blinding_factors, void* const* z_devs) {
+    ENTER; return permutation_product_circuits(ctx, values, sigmas, n_columns, n_circuits, chunk_len, k, beta, gamma, blinding, blinding_factors, z_devs);
+}
+extern "C" {
 int zk_lookup_product_batch_dev(zk_ctx* ctx, const void* const* cols4, size_t count, uint32_t k, const void* beta, const void* gamma, const void* blinding,
                                 uint32_t blinding_factors, void* const* z_devs) ZK_ABI_TRY {
     ENTER; return lookup_product_batch(ctx, cols4, count, k, beta, gamma, blinding, blinding_factors, z_devs);
@@ -519,31 +528,43 @@ int zk_quotient_program_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_prog, u
 // ABI versioning (zkmi355.h): the caller's sizeof of a boundary struct must be this build's before any other field is read
 #define ARGS_SIZE(fn) do { if (!args) return ctx->fail(ZK_ERR_ARG, fn ": null args"); \
         if (args->struct_size != sizeof(zk_quotient_args)) return ctx->fail(ZK_ERR_ARG, fn ": zk_quotient_args.struct_size %u, expected %zu (ABI version %u)", args->struct_size, sizeof(zk_quotient_args), ZK_ABI_VERSION); } while (0)
-int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 0, 0); } ZK_ABI_CATCH(ctx)
+int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 0, 0, 0); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset) ZK_ABI_TRY {
     ENTER;
     ARGS_SIZE("zk_quotient_run_coset_dev");
     if (coset >= (1u << 16)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_dev: coset %u out of range", coset);
-    return quotient_run(ctx, prog, args, (int)coset, 0, 0, 0, 0);
+    return quotient_run(ctx, prog, args, (int)coset, 0, 0, 0, 0, 0);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_rows_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint64_t row_lo, uint64_t row_count) ZK_ABI_TRY {
     ENTER;
     ARGS_SIZE("zk_quotient_run_coset_rows_dev");
     if (coset >= (1u << 16)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_rows_dev: coset %u out of range", coset);
     if (!row_count) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_rows_dev: row_count = 0");
-    return quotient_run(ctx, prog, args, (int)coset, row_lo, row_count, 0, 0);
+    return quotient_run(ctx, prog, args, (int)coset, row_lo, row_count, 0, 0, 0);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low) ZK_ABI_TRY { ENTER; return quotient_program_split(ctx, prog, low_cosets, n_instr_high, n_instr_low); } ZK_ABI_CATCH(ctx)
-int zk_quotient_run_high_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_high_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 1, 0); } ZK_ABI_CATCH(ctx)
+int zk_quotient_run_high_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_high_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 1, 0, 0); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_low_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t low_cosets) ZK_ABI_TRY {
     ENTER; ARGS_SIZE("zk_quotient_run_low_dev");
     if (!low_cosets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_low_dev: low_cosets = 0");
-    return quotient_run(ctx, prog, args, -1, 0, 0, 2, low_cosets);
+    return quotient_run(ctx, prog, args, -1, 0, 0, 2, low_cosets, 0);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_part_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part) ZK_ABI_TRY {
     ENTER; ARGS_SIZE("zk_quotient_run_coset_part_dev");
     if (coset >= (1u << 16) || part < 1 || part > 2) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_part_dev: coset %u / part %u out of range", coset, part);
-    return quotient_run(ctx, prog, args, (int)coset, 0, 0, (int)part, 0);
+    return quotient_run(ctx, prog, args, (int)coset, 0, 0, (int)part, 0, 0);
+} ZK_ABI_CATCH(ctx)
+// halo2's fold across the circuits of one proof: out <- out * y^E + numerator (coset = UINT32_MAX: the whole extended domain; part 2 there: the program's low cosets)
+int zk_quotient_run_acc_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part) ZK_ABI_TRY {
+    ENTER; ARGS_SIZE("zk_quotient_run_acc_dev");
+    if ((coset != UINT32_MAX && coset >= (1u << 16)) || part > 2) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_acc_dev: coset %u / part %u out of range", coset, part);
+    uint32_t low_cosets = 0;
+    if (coset == UINT32_MAX && part == 2) {
+        int rc = quotient_program_split(ctx, prog, &low_cosets, nullptr, nullptr);
+        if (rc) return rc;
+        if (!low_cosets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_acc_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
+    }
+    return quotient_run(ctx, prog, args, coset == UINT32_MAX ? -1 : (int)coset, 0, 0, (int)part, low_cosets, 1);
 } ZK_ABI_CATCH(ctx)
 
 int zk_pk_load(zk_ctx* ctx, uint64_t prog, const void* const* fixed, const void* const* sigma, const void* l0, const void* l_last, const void* l_active,

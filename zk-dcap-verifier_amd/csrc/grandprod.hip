@@ -194,10 +194,11 @@ static u256 gp_rd(const void* p) { u256 o; memcpy(&o, p, 32); return o; }
 // per workgroup is paid once, not once per column), the prefix products of every column, and the assembly.  chain: the columns are the sets of
 // one permutation argument, z_s[0] = z_(s-1)[n - bf - 1] with the first set at init — every set is scanned from 1, the few chaining products are
 // done on the host from two downloaded values per set, and the assemble pass applies them; otherwise every column starts at init.
-// blinding: count x bf x 32 B; h_last_z (optional) <- z[n - bf - 1] of the last column.  Needs bf + 2 <= n.
+// blinding: count x bf x 32 B; h_last_z (optional) <- z[n - bf - 1] of the last column.  Needs bf + 2 <= n.  chain_len > 0: the chain restarts at init every chain_len
+// columns (the permutation arguments of several circuits in one batch).
 template <class Fractions>
 static int gp_products(zk_ctx* ctx, size_t count, uint32_t n, const u256& init, bool chain, const void* blinding, uint32_t bf, void* const* d_zs, void* h_last_z,
-                       size_t extra_bytes, Fractions fractions) {
+                       size_t extra_bytes, Fractions fractions, size_t chain_len = 0) {
     const uint32_t span = GP_T * GP_E, nblocks = (n + span - 1) / span;     // scan workgroups per column
     const size_t N = count * (size_t)n;
     size_t off = 0;
@@ -231,7 +232,7 @@ static int gp_products(zk_ctx* ctx, size_t count, uint32_t n, const u256& init, 
             ZK_HIP(hipMemcpyAsync(&pre[s], base + o_tot + (s * (size_t)nblocks + src / span) * 32, 32, hipMemcpyDeviceToHost, st));
         }
         ZK_HIP(hipStreamSynchronize(st));
-        for (size_t s = 1; s < count; s++) inits[s] = Fr::mul(inits[s - 1], Fr::mul(loc[s - 1], pre[s - 1]));
+        for (size_t s = 1; s < count; s++) if (!chain_len || s % chain_len) inits[s] = Fr::mul(inits[s - 1], Fr::mul(loc[s - 1], pre[s - 1]));
     }
     ZK_HIP(hipMemcpyAsync(base + o_in, inits.data(), count * 32, hipMemcpyHostToDevice, st));
     ZK_LAUNCH(gp_assemble_batch_kernel, dim3((n + blk - 1) / blk, (uint32_t)count), blk, 0, st, (const void*)(base + o_num), (const void*)(base + o_tot), n, n - bf,
@@ -244,8 +245,10 @@ static int gp_products(zk_ctx* ctx, size_t count, uint32_t n, const u256& init, 
 
 // The permutation argument (permutation::Argument::commit's loop over chunks): m columns in sets of chunk_len; the delta powers continue across the
 // sets from delta_start (the first column's), z of the first set starts at z_init.  The callers have checked the arguments.
+// circuits > 1: values hold circuits x m columns (circuit-major) against the same m sigmas, and every circuit's sets form a chain of their own (d_zs: circuits x n_sets).
 static int gp_permutation(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
-                          const void* gamma, const u256& delta_start, const u256& z_init, const void* blinding, uint32_t bf, void* const* d_zs, void* h_last_z) {
+                          const void* gamma, const u256& delta_start, const u256& z_init, const void* blinding, uint32_t bf, void* const* d_zs, void* h_last_z,
+                          size_t circuits = 1) {
     const uint32_t n = 1u << k;
     const size_t n_sets = (m + chunk_len - 1) / chunk_len;
     const uint64_t dl[4] = BN254_FR_DELTA_M;
@@ -257,23 +260,25 @@ static int gp_permutation(zk_ctx* ctx, const void* const* values, const void* co
     int rc = ntt_pow_tables(ctx, k, domain_omega(k), &a.tw_lo, &a.tw_hi, &a.lo_bits);
     if (rc) return rc;
     const int blk = ctx->tune.vec_block;
-    return gp_products(ctx, n_sets, n, z_init, true, blinding, bf, d_zs, h_last_z, 0, [&](char* num, char* den, char*) -> int {
-        u256 cur = Fr::mul(delta_start, a.beta);                     // delta^j * beta, continuing across the sets
-        for (size_t s = 0; s < n_sets; s++) {
-            const size_t lo = s * chunk_len, cnt = std::min<size_t>(chunk_len, m - lo);
-            a.count = (uint32_t)cnt;
-            for (size_t j = 0; j < cnt; j++) {
-                a.values[j] = values[lo + j]; a.sigmas[j] = sigmas[lo + j];
-                a.delta_beta[j] = cur;
-                cur = Fr::mul(cur, delta);
+    return gp_products(ctx, circuits * n_sets, n, z_init, true, blinding, bf, d_zs, h_last_z, 0, [&](char* num, char* den, char*) -> int {
+        for (size_t c = 0; c < circuits; c++) {
+            u256 cur = Fr::mul(delta_start, a.beta);                 // delta^j * beta, continuing across the sets of one circuit
+            for (size_t s = 0; s < n_sets; s++) {
+                const size_t lo = s * chunk_len, cnt = std::min<size_t>(chunk_len, m - lo), at = c * n_sets + s;
+                a.count = (uint32_t)cnt;
+                for (size_t j = 0; j < cnt; j++) {
+                    a.values[j] = values[c * m + lo + j]; a.sigmas[j] = sigmas[lo + j];
+                    a.delta_beta[j] = cur;
+                    cur = Fr::mul(cur, delta);
+                }
+                a.num = num + at * (size_t)n * 32;
+                a.den = den + at * (size_t)n * 32;
+                ZK_LAUNCH(gp_perm_fraction_kernel, (n + blk - 1) / blk, blk, 0, ctx->stream, a);
+                ZK_CHECK_LAUNCH();
             }
-            a.num = num + s * (size_t)n * 32;
-            a.den = den + s * (size_t)n * 32;
-            ZK_LAUNCH(gp_perm_fraction_kernel, (n + blk - 1) / blk, blk, 0, ctx->stream, a);
-            ZK_CHECK_LAUNCH();
         }
         return ZK_OK;
-    });
+    }, circuits > 1 ? n_sets : 0);
 }
 
 int permutation_product(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t count, uint32_t k, const void* beta, const void* gamma,
@@ -301,6 +306,20 @@ int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* 
     for (size_t j = 0; j < m; j++)
         if (!values[j] || !sigmas[j]) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null column %zu", j);
     return gp_permutation(ctx, values, sigmas, m, chunk_len, k, beta, gamma, Fr::one(), Fr::one(), blinding, bf, d_zs, nullptr);
+}
+
+// The permutation arguments of several circuits that share a key (one proof over n_circuits circuits): values = n_circuits x m columns, circuit-major; sigmas = m;
+// d_zs = n_circuits x n_sets, blinding likewise.  One launch sequence for all of them; every circuit's sets chain on their own, exactly as permutation_product_all per circuit.
+int permutation_product_circuits(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, size_t n_circuits, uint32_t chunk_len, uint32_t k,
+                                 const void* beta, const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs) {
+    if (m == 0 || n_circuits == 0) return ZK_OK;
+    if (!values || !sigmas || !beta || !gamma || !d_zs || (bf && !blinding) || chunk_len == 0) return ctx->fail(ZK_ERR_ARG, "permutation products of several circuits: null argument");
+    if (chunk_len > (uint32_t)GP_MAX_COLS) return ctx->fail(ZK_ERR_LIMIT, "permutation products of several circuits: %u columns per set (max %d)", chunk_len, GP_MAX_COLS);
+    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "permutation products of several circuits: k = %u out of range", k);
+    const uint32_t n = 1u << k;
+    if (bf + 2 >= n) return ctx->fail(ZK_ERR_ARG, "permutation products of several circuits: blinding_factors too large");
+    for (size_t j = 0; j < m * n_circuits; j++) if (!values[j] || !sigmas[j % m]) return ctx->fail(ZK_ERR_ARG, "permutation products of several circuits: null column %zu", j);
+    return gp_permutation(ctx, values, sigmas, m, chunk_len, k, beta, gamma, Fr::one(), Fr::one(), blinding, bf, d_zs, nullptr, n_circuits);
 }
 
 // All lookup grand products of a proof in one launch sequence (Permuted::commit_product for every lookup); cols4 = [cin, ctab, pin, ptab] per lookup.

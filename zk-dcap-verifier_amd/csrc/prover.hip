@@ -4,7 +4,8 @@
 // O(n) step is one of the zk_* entry points the Rust prover would call, in the order of INTEGRATION.md's phase table; what stays on the host is what
 // stays on the host in the reference — Fiat-Shamir hashing (Blake2b, src/transcript.rs), point encoding, rotation-set bookkeeping and the O(#points^2)
 // interpolations of SHPLONK.  zk-dcap-verifier_amd/plonk/prover.py + shplonk.py are the Python twin (phase by phase, draw by draw): both must emit the
-// bytes of the independent CPU prover's goldens (tests/test_native_prover.py).  Single circuit instance, no user challenges, Blake2b transcript (stack A).
+// bytes of the independent CPU prover's goldens (tests/test_native_prover.py).  One circuit instance or several (zk_plonk_create_proof_multi: one proof over m circuits
+// that share the key, halo2's `&[c0, c1, ..]`), no user challenges, Blake2b transcript (stack A).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -29,6 +30,8 @@ using namespace zk;
 int zk_internal_fail(zk_ctx* ctx, int code, const char* msg);   // capi.hip: sets zk_last_error(ctx)
 zk_ctx* zk_internal_helper_ctx(zk_ctx* ctx);                      // capi.hip: the helper context of ctx (ctx.h), or null
 void zk_internal_trim_helper(zk_ctx* ctx);                        // capi.hip: give the helper context's grow-only device memory back (zk_plonk_trim)
+int zk_internal_permutation_products(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t n_columns, size_t n_circuits, uint32_t chunk_len, uint32_t k,
+                                     const void* beta, const void* gamma, const void* blinding, uint32_t blinding_factors, void* const* z_devs);   // capi.hip: the m-circuit permutation products
 
 namespace {
 int pk_fail(zk_ctx* ctx, int code, const char* fmt, ...) {
@@ -474,7 +477,7 @@ struct ShardSignal {
 };
 static const uint64_t POISON[4] = {~0ull, ~0ull, ~0ull, ~0ull};
 
-static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void* const* advice, int advice_on_device, const void* const* instances,
+static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t m, const void* const* advice, int advice_on_device, const void* const* instances,
                              const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len, ShardSignal& sig);
 
 // proofs this process has in flight (every device together: a prover process drives one GPU): the side lane fills a lone proof's idle issue slots — with three and more
@@ -482,15 +485,15 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
 static std::atomic<int> g_proofs_in_flight{0};
 struct InFlight { InFlight() { g_proofs_in_flight.fetch_add(1); } ~InFlight() { g_proofs_in_flight.fetch_sub(1); } };
 
-extern "C" int zk_plonk_create_proof(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void* const* advice, int advice_on_device, const void* const* instances,
-                                     const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+static int create_proof_entry(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t m, const void* const* advice, int advice_on_device, const void* const* instances,
+                              const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) {
     if (!ctx || !pk) return ZK_ERR_ARG;
     InFlight counted;
     Arena xmem(ctx);                                                   // (before the body's own arena: a failing body has returned everything else when the poisoned block travels)
     ShardSignal sig;
     sig.xmem = &xmem;
     int rc;
-    try { rc = create_proof_body(ctx, pk, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len, sig); }
+    try { rc = create_proof_body(ctx, pk, m, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len, sig); }
     catch (...) { rc = abi_exception(ctx, "zk_plonk_create_proof"); }   // (here rather than at the barrier below: the other ranks of a sharded proof are told first)
     if (rc != ZK_OK && rc != ZK_ERR_COMM && sig.armed && sig.next < sig.sizes.size()) {
         std::string why = zk_last_error(ctx) ? zk_last_error(ctx) : "";
@@ -499,11 +502,28 @@ extern "C" int zk_plonk_create_proof(zk_ctx* ctx, const zk_plonk_pk_desc* pk, co
         pk_fail(ctx, rc, "%s [rank %u of a sharded proof: failure signalled to the other ranks in exchange %zu]", why.c_str(), pk->shard_rank, sig.next);
     }
     return rc;
+}
+
+extern "C" int zk_plonk_create_proof(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void* const* advice, int advice_on_device, const void* const* instances,
+                                     const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+    return create_proof_entry(ctx, pk, 1, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
 } ZK_ABI_CATCH(ctx)
 
-static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void* const* advice, int advice_on_device, const void* const* instances,
-                             const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len, ShardSignal& sig) {
+// halo2's create_proof over a slice of circuits: one proof, one vanishing argument, one SHPLONK opening for all of them (m = 1: zk_plonk_create_proof)
+extern "C" int zk_plonk_create_proof_multi(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t n_circuits, const void* const* advice, int advice_on_device,
+                                           const void* const* instances, const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user,
+                                           void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
     if (!ctx || !pk) return ZK_ERR_ARG;
+    if (!n_circuits) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof_multi: n_circuits = 0");
+    return create_proof_entry(ctx, pk, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+} ZK_ABI_CATCH(ctx)
+
+// m circuits that share the key (m = 1: the single-circuit proof, byte for byte).  Where halo2 loops over the circuits ([3P-MEM] plonk/prover.rs, evaluation.rs), so do
+// the transcript and the draws: per circuit in order 0 .. m-1; what the key holds (fixed, sigma, l0 / l_last / l_active_row) and the vanishing argument exist once.  Every
+// phase gathers the columns of all m circuits into its batched launch; the quotient runs per (circuit, coset or part), circuit 0 plain and the others in accumulate mode.
+static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t m, const void* const* advice, int advice_on_device, const void* const* instances,
+                             const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len, ShardSignal& sig) {
+    if (!ctx || !pk || !m) return ZK_ERR_ARG;
     if (pk->struct_size != sizeof(zk_plonk_pk_desc))
         return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof: zk_plonk_pk_desc.struct_size %u, expected %zu (ABI version %u)", pk->struct_size, sizeof(zk_plonk_pk_desc), ZK_ABI_VERSION);
     if (!rng || !proof_len || (pk->n_advice && !advice)) return ZK_ERR_ARG;
@@ -517,6 +537,8 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     // the descriptor is the caller's: refuse indices that would read outside its arrays
     const uint32_t world = pk->shard_world > 1 ? pk->shard_world : 1, rank = world > 1 ? pk->shard_rank : 0;
     const bool sharded = world > 1;
+    if (sharded && m > 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof_multi: %u circuits on a sharded key (shard_world %u): one proof over several circuits runs on one GPU", m, world);
+    const uint32_t A = pk->n_advice, I = pk->n_instance;              // per circuit; circuit c's columns are [c * A, (c + 1) * A) etc. (circuit-major)
     if ((pk->n_fixed && (!pk->fixed_values || !pk->fixed_polys)) || (pk->n_perm_columns && (!pk->perm_columns || !pk->sigma_values || !pk->sigma_polys)) ||
         (L && (!pk->lookup_input_programs || !pk->lookup_table_programs || !pk->lookup_table_key)) || (pk->n_advice_queries && !pk->advice_queries) ||
         (pk->n_fixed_queries && !pk->fixed_queries) || !pk->transcript_repr)
@@ -551,7 +573,7 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     }
     for (uint32_t i = 0; i < pk->n_advice_queries; i++) if (pk->advice_queries[2 * i] >= pk->n_advice) return ZK_ERR_ARG;
     for (uint32_t i = 0; i < pk->n_fixed_queries; i++) if (pk->fixed_queries[2 * i] >= pk->n_fixed) return ZK_ERR_ARG;
-    for (uint32_t i = 0; i < pk->n_advice; i++) if (!advice[i]) return ZK_ERR_ARG;
+    for (size_t i = 0; i < (size_t)m * A; i++) if (!advice[i]) return ZK_ERR_ARG;
     Arena mem(ctx);
     SideLane lane;                                                     // (after the arena: its destructor joins the helper thread before the buffers go back to the pool)
     if (pk->transcript > 2) return ZK_ERR_ARG;
@@ -595,21 +617,25 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     // permute_expression_pair's input rows then table rows, then commit_values' two Blinds; per permutation set its rows + one Blind; per lookup product its rows + one Blind; the
     // vanishing argument's n coefficients + one Blind; one Blind per h(X) piece.
     if (pk->draw_schedule != 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof: draw_schedule %u (1 = halo2_proofs v2023_01_20, the only schedule this build knows)", pk->draw_schedule);
+    // m circuits: each per-circuit block below runs for circuit 0, 1, .., m-1 in turn (circuit c + 1's advice draws start after circuit c's Blinds); the vanishing argument once.
     auto plan = [&](size_t count) { draws.counts.push_back(count); return draws.counts.size() - 1; };
-    std::vector<size_t> d_bi(L), d_bt(L), d_pb(n_sets), d_lb(L);
-    for (uint32_t i = 0; i < pk->n_advice; i++) plan(n - usable);                                  // items [0, n_advice)
-    for (uint32_t i = 0; i < pk->n_advice; i++) plan(1);
-    for (uint32_t l = 0; l < L; l++) { d_bi[l] = plan(bf + 1); d_bt[l] = plan(bf + 1); plan(1); plan(1); }
-    for (uint32_t s = 0; s < n_sets; s++) { d_pb[s] = plan(bf); plan(1); }
-    for (uint32_t l = 0; l < L; l++) { d_lb[l] = plan(bf); plan(1); }
+    const size_t mA = (size_t)m * A, mI = (size_t)m * I, mL = (size_t)m * L, mS = (size_t)m * n_sets;
+    std::vector<size_t> d_ar(mA), d_bi(mL), d_bt(mL), d_pb(mS), d_lb(mL);
+    for (uint32_t c = 0; c < m; c++) {
+        for (uint32_t i = 0; i < A; i++) d_ar[(size_t)c * A + i] = plan(n - usable);                // (m = 1: items [0, n_advice))
+        for (uint32_t i = 0; i < A; i++) plan(1);
+    }
+    for (size_t cl = 0; cl < mL; cl++) { d_bi[cl] = plan(bf + 1); d_bt[cl] = plan(bf + 1); plan(1); plan(1); }
+    for (size_t cs = 0; cs < mS; cs++) { d_pb[cs] = plan(bf); plan(1); }
+    for (size_t cl = 0; cl < mL; cl++) { d_lb[cl] = plan(bf); plan(1); }
     const size_t d_rp = plan(n);
     for (uint32_t i = 0; i < 1 + n_pieces; i++) plan(1);
     draws.start(rng, rng_user, mem.pool);
 
     // ---- 1. vk, instances ----------------------------------------------------------------------------------------------------------------------------
     tr.common_scalar(Fr::to_mont(load32(pk->transcript_repr)));
-    std::vector<void*> inst_values;
-    for (uint32_t c = 0; c < pk->n_instance; c++) {
+    std::vector<void*> inst_values;                                   // m x n_instance, circuit-major
+    for (size_t c = 0; c < mI; c++) {
         const uint32_t len = instance_lens ? instance_lens[c] : 0;
         if (len > usable || (len && (!instances || !instances[c]))) return ZK_ERR_ARG;
         std::vector<uint64_t> col((size_t)len * 4);
@@ -628,19 +654,19 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     }
     clk.lap(0);
     // ---- 2. advice: upload (host columns), blind, commit ------------------------------------------------------------------------------------------------
-    std::vector<void*> adv(pk->n_advice);
+    std::vector<void*> adv(mA);                                       // m x n_advice, circuit-major
     {
         std::vector<void*> dst;
         std::vector<const void*> src;
-        for (uint32_t i = 0; i < pk->n_advice; i++) {
+        for (size_t i = 0; i < mA; i++) {
             if (advice_on_device) adv[i] = (void*)advice[i];
             else { adv[i] = mem.get(col_bytes); if (!adv[i]) return ZK_ERR_HIP; dst.push_back(adv[i]); src.push_back(advice[i]); }
         }
         if (!dst.empty()) PK(zk_dev_upload_batch(ctx, dst.data(), src.data(), dst.size(), col_bytes));
-        std::vector<void*> bdst(pk->n_advice);
-        std::vector<const void*> bsrc(pk->n_advice);
-        for (uint32_t i = 0; i < pk->n_advice; i++) { bdst[i] = (char*)adv[i] + usable * 32; bsrc[i] = draws.take(i); }
-        if (pk->n_advice) PK(zk_dev_upload_batch(ctx, bdst.data(), bsrc.data(), pk->n_advice, (n - usable) * 32));
+        std::vector<void*> bdst(mA);
+        std::vector<const void*> bsrc(mA);
+        for (size_t i = 0; i < mA; i++) { bdst[i] = (char*)adv[i] + usable * 32; bsrc[i] = draws.take(d_ar[i]); }
+        if (mA) PK(zk_dev_upload_batch(ctx, bdst.data(), bsrc.data(), mA, (n - usable) * 32));
     }
     // the side lane (SideLane above): a single-GPU proof on the extended domain hands every phase's columns to the helper context as soon as their values are final
     bool side = false;
@@ -689,72 +715,77 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
         for (size_t i = 0; i < cols.size(); i++) tr.write_point(&out[12 * i]);
         return ZK_OK;
     };
-    PK(commit(pk->srs_g_lagrange, adv));
+    PK(commit(pk->srs_g_lagrange, adv));                               // (one batch: the m x n_advice commitments, circuit by circuit in the transcript)
     clk.lap(1);
     // ---- 3. theta; lookups: compress, permute, commit ---------------------------------------------------------------------------------------------------
     const Fe theta = tr.squeeze();
     const Fe one = Fr::one();
-    std::vector<void*> cin(L), ctab(L);
+    std::vector<void*> cin(mL), ctab(mL);                              // m x n_lookups, circuit-major (as pin / ptab / lzs below)
     {
-        const void* anycol = pk->n_fixed ? pk->fixed_values[0] : (pk->n_advice ? adv[0] : nullptr);
-        std::map<uint32_t, void*> table_cache;
-        auto compress = [&](uint64_t prog, void** out) -> int {
-            *out = mem.get(col_bytes);
-            if (!*out) return ZK_ERR_HIP;
-            zk_quotient_args a;
-            ZK_STRUCT_INIT(a);
-            a.fixed = pk->fixed_values; a.advice = (const void* const*)adv.data(); a.instance = (const void* const*)inst_values.data();
-            a.l0 = a.l_last = a.l_active_row = anycol;
-            a.beta = a.gamma = a.y = one.v; a.theta = theta.v; a.challenges = one.v;
-            a.out = *out;
-            return zk_quotient_run_dev(ctx, prog, &a);
-        };
-        for (uint32_t l = 0; l < L; l++) {
-            auto it = table_cache.find(pk->lookup_table_key[l]);
-            if (it == table_cache.end()) { void* t = nullptr; PK(compress(pk->lookup_table_programs[l], &t)); it = table_cache.emplace(pk->lookup_table_key[l], t).first; }
-            PK(compress(pk->lookup_input_programs[l], &cin[l]));
-            ctab[l] = it->second;
+        std::map<std::pair<uint32_t, uint32_t>, void*> table_cache;     // (circuit, table key): a table expression may read the circuit's own columns
+        for (uint32_t c = 0; c < m; c++) {
+            const void* anycol = pk->n_fixed ? pk->fixed_values[0] : (A ? adv[(size_t)c * A] : nullptr);
+            auto compress = [&](uint64_t prog, void** out) -> int {
+                *out = mem.get(col_bytes);
+                if (!*out) return ZK_ERR_HIP;
+                zk_quotient_args a;
+                ZK_STRUCT_INIT(a);
+                a.fixed = pk->fixed_values; a.advice = (const void* const*)adv.data() + (size_t)c * A; a.instance = (const void* const*)inst_values.data() + (size_t)c * I;
+                a.l0 = a.l_last = a.l_active_row = anycol;
+                a.beta = a.gamma = a.y = one.v; a.theta = theta.v; a.challenges = one.v;
+                a.out = *out;
+                return zk_quotient_run_dev(ctx, prog, &a);
+            };
+            for (uint32_t l = 0; l < L; l++) {
+                const size_t cl = (size_t)c * L + l;
+                auto it = table_cache.find({c, pk->lookup_table_key[l]});
+                if (it == table_cache.end()) { void* t = nullptr; PK(compress(pk->lookup_table_programs[l], &t)); it = table_cache.emplace(std::make_pair(c, pk->lookup_table_key[l]), t).first; }
+                PK(compress(pk->lookup_input_programs[l], &cin[cl]));
+                ctab[cl] = it->second;
+            }
         }
     }
-    std::vector<void*> pin(L), ptab(L);
-    if (L) {
-        std::vector<uint64_t> bi((size_t)L * (bf + 1) * 4), bt((size_t)L * (bf + 1) * 4);
-        for (uint32_t l = 0; l < L; l++) {
-            memcpy(&bi[(size_t)l * (bf + 1) * 4], draws.take(d_bi[l]), (bf + 1) * 32);
-            memcpy(&bt[(size_t)l * (bf + 1) * 4], draws.take(d_bt[l]), (bf + 1) * 32);
+    std::vector<void*> pin(mL), ptab(mL);
+    if (mL) {
+        std::vector<uint64_t> bi(mL * (bf + 1) * 4), bt(mL * (bf + 1) * 4);
+        for (size_t cl = 0; cl < mL; cl++) {
+            memcpy(&bi[cl * (bf + 1) * 4], draws.take(d_bi[cl]), (bf + 1) * 32);
+            memcpy(&bt[cl * (bf + 1) * 4], draws.take(d_bt[cl]), (bf + 1) * 32);
         }
-        for (uint32_t l = 0; l < L; l++) { pin[l] = mem.get(col_bytes); ptab[l] = mem.get(col_bytes); if (!pin[l] || !ptab[l]) return ZK_ERR_HIP; }
-        PK(zk_lookup_permute_batch_dev(ctx, (const void* const*)cin.data(), (const void* const*)ctab.data(), L, k, bf, bi.data(), bt.data(), pin.data(), ptab.data()));
+        for (size_t cl = 0; cl < mL; cl++) { pin[cl] = mem.get(col_bytes); ptab[cl] = mem.get(col_bytes); if (!pin[cl] || !ptab[cl]) return ZK_ERR_HIP; }
+        PK(zk_lookup_permute_batch_dev(ctx, (const void* const*)cin.data(), (const void* const*)ctab.data(), mL, k, bf, bi.data(), bt.data(), pin.data(), ptab.data()));
         std::vector<void*> flat;
-        for (uint32_t l = 0; l < L; l++) { flat.push_back(pin[l]); flat.push_back(ptab[l]); }
+        for (size_t cl = 0; cl < mL; cl++) { flat.push_back(pin[cl]); flat.push_back(ptab[cl]); }
         if (side) PK(early(flat, coefB, extB));
         PK(commit(pk->srs_g_lagrange, flat));
     }
     clk.lap(2);
     // ---- 4. beta, gamma; grand products -------------------------------------------------------------------------------------------------------------------
     const Fe beta = tr.squeeze(), gamma = tr.squeeze();
-    std::vector<void*> zs(n_sets), lzs(L);
+    std::vector<void*> zs(mS), lzs(mL);
     if (n_sets) {
-        std::vector<const void*> vals(pk->n_perm_columns);
-        for (uint32_t j = 0; j < pk->n_perm_columns; j++) {
-            const uint32_t ty = pk->perm_columns[2 * j], ix = pk->perm_columns[2 * j + 1];
-            vals[j] = ty == 0 ? adv[ix] : ty == 1 ? pk->fixed_values[ix] : inst_values[ix];
-        }
-        std::vector<uint64_t> blind((size_t)n_sets * bf * 4);
-        for (uint32_t s = 0; s < n_sets; s++) memcpy(&blind[(size_t)s * bf * 4], draws.take(d_pb[s]), bf * 32);
-        for (uint32_t s = 0; s < n_sets; s++) { zs[s] = mem.get(col_bytes); if (!zs[s]) return ZK_ERR_HIP; }
-        PK(zk_permutation_product_all_dev(ctx, vals.data(), pk->sigma_values, pk->n_perm_columns, chunk, k, beta.v, gamma.v, blind.data(), bf, zs.data()));
+        std::vector<const void*> vals((size_t)m * pk->n_perm_columns);
+        for (uint32_t c = 0; c < m; c++)
+            for (uint32_t j = 0; j < pk->n_perm_columns; j++) {
+                const uint32_t ty = pk->perm_columns[2 * j], ix = pk->perm_columns[2 * j + 1];
+                vals[(size_t)c * pk->n_perm_columns + j] = ty == 0 ? adv[(size_t)c * A + ix] : ty == 1 ? pk->fixed_values[ix] : inst_values[(size_t)c * I + ix];
+            }
+        std::vector<uint64_t> blind(mS * bf * 4);
+        for (size_t cs = 0; cs < mS; cs++) memcpy(&blind[cs * bf * 4], draws.take(d_pb[cs]), bf * 32);
+        for (size_t cs = 0; cs < mS; cs++) { zs[cs] = mem.get(col_bytes); if (!zs[cs]) return ZK_ERR_HIP; }
+        if (m == 1) PK(zk_permutation_product_all_dev(ctx, vals.data(), pk->sigma_values, pk->n_perm_columns, chunk, k, beta.v, gamma.v, blind.data(), bf, zs.data()));
+        else PK(zk_internal_permutation_products(ctx, vals.data(), pk->sigma_values, pk->n_perm_columns, m, chunk, k, beta.v, gamma.v, blind.data(), bf, zs.data()));
     }
-    if (L) {
+    if (mL) {
         std::vector<const void*> quads;
-        for (uint32_t l = 0; l < L; l++) { quads.push_back(cin[l]); quads.push_back(ctab[l]); quads.push_back(pin[l]); quads.push_back(ptab[l]); }
-        std::vector<uint64_t> blind((size_t)L * bf * 4);
-        for (uint32_t l = 0; l < L; l++) memcpy(&blind[(size_t)l * bf * 4], draws.take(d_lb[l]), bf * 32);
-        for (uint32_t l = 0; l < L; l++) { lzs[l] = mem.get(col_bytes); if (!lzs[l]) return ZK_ERR_HIP; }
-        PK(zk_lookup_product_batch_dev(ctx, quads.data(), L, k, beta.v, gamma.v, blind.data(), bf, lzs.data()));
+        for (size_t cl = 0; cl < mL; cl++) { quads.push_back(cin[cl]); quads.push_back(ctab[cl]); quads.push_back(pin[cl]); quads.push_back(ptab[cl]); }
+        std::vector<uint64_t> blind(mL * bf * 4);
+        for (size_t cl = 0; cl < mL; cl++) memcpy(&blind[cl * bf * 4], draws.take(d_lb[cl]), bf * 32);
+        for (size_t cl = 0; cl < mL; cl++) { lzs[cl] = mem.get(col_bytes); if (!lzs[cl]) return ZK_ERR_HIP; }
+        PK(zk_lookup_product_batch_dev(ctx, quads.data(), mL, k, beta.v, gamma.v, blind.data(), bf, lzs.data()));
     }
     {
-        std::vector<void*> both(zs);
+        std::vector<void*> both(zs);                                  // every circuit's permutation products, then every circuit's lookup products (halo2's two loops)
         both.insert(both.end(), lzs.begin(), lzs.end());
         if (side) PK(early(both, coefC, extC));
         PK(commit(pk->srs_g_lagrange, both));
@@ -769,6 +800,7 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     // ---- 6. y; coefficient form; extended cosets; h(X) numerator ----------------------------------------------------------------------------------------------
     const Fe y = tr.squeeze();
     std::vector<void*> side_ext;
+    std::map<void*, void*> ext_of;                                    // side lane: coefficient form -> extended form
     if (side) {                                                       // the helper context has brought every column to both forms: from here on the vectors name the coefficient forms
         const int rc_side = lane.wait();
         if (rc_side) return pk_fail(ctx, rc_side, "zk_plonk_create_proof: transforms on the helper context: %s", zk_last_error(lane.h));
@@ -779,18 +811,24 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
         for (void* p : inst_values) mem.give_back(p);
         for (void* p : zs) mem.give_back(p);
         for (void* p : lzs) mem.give_back(p);
-        for (uint32_t l = 0; l < L; l++) { mem.give_back(pin[l]); mem.give_back(ptab[l]); mem.give_back(cin[l]); mem.give_back(ctab[l]); }
-        for (uint32_t i = 0; i < pk->n_advice; i++) { adv[i] = coefA[i]; side_ext.push_back(extA[i]); }
-        for (uint32_t c = 0; c < pk->n_instance; c++) { inst_values[c] = coefA[pk->n_advice + c]; side_ext.push_back(extA[pk->n_advice + c]); }
-        for (uint32_t s_ = 0; s_ < n_sets; s_++) { zs[s_] = coefC[s_]; side_ext.push_back(extC[s_]); }
-        for (uint32_t l = 0; l < L; l++) { lzs[l] = coefC[n_sets + l]; side_ext.push_back(extC[n_sets + l]); }
-        for (uint32_t l = 0; l < L; l++) { pin[l] = coefB[2 * l]; ptab[l] = coefB[2 * l + 1]; side_ext.push_back(extB[2 * l]); side_ext.push_back(extB[2 * l + 1]); }
+        for (size_t cl = 0; cl < mL; cl++) { mem.give_back(pin[cl]); mem.give_back(ptab[cl]); mem.give_back(cin[cl]); mem.give_back(ctab[cl]); }
+        for (size_t i = 0; i < mA; i++) { adv[i] = coefA[i]; ext_of[coefA[i]] = extA[i]; }
+        for (size_t c = 0; c < mI; c++) { inst_values[c] = coefA[mA + c]; ext_of[coefA[mA + c]] = extA[mA + c]; }
+        for (size_t s_ = 0; s_ < mS; s_++) { zs[s_] = coefC[s_]; ext_of[coefC[s_]] = extC[s_]; }
+        for (size_t cl = 0; cl < mL; cl++) { lzs[cl] = coefC[mS + cl]; ext_of[coefC[mS + cl]] = extC[mS + cl]; }
+        for (size_t cl = 0; cl < mL; cl++) { pin[cl] = coefB[2 * cl]; ptab[cl] = coefB[2 * cl + 1]; ext_of[coefB[2 * cl]] = extB[2 * cl]; ext_of[coefB[2 * cl + 1]] = extB[2 * cl + 1]; }
     }
-    std::vector<void*> lag(adv);
-    lag.insert(lag.end(), inst_values.begin(), inst_values.end());
-    lag.insert(lag.end(), zs.begin(), zs.end());
-    lag.insert(lag.end(), lzs.begin(), lzs.end());
-    for (uint32_t l = 0; l < L; l++) { lag.push_back(pin[l]); lag.push_back(ptab[l]); }
+    // the proof's columns, one block of W per circuit in the order the quotient's arguments take them: advice, instance, permutation products, lookup products, permuted pairs
+    const size_t W = (size_t)A + I + n_sets + 3 * (size_t)L;
+    std::vector<void*> lag;
+    for (uint32_t c = 0; c < m; c++) {
+        lag.insert(lag.end(), adv.begin() + (size_t)c * A, adv.begin() + (size_t)(c + 1) * A);
+        lag.insert(lag.end(), inst_values.begin() + (size_t)c * I, inst_values.begin() + (size_t)(c + 1) * I);
+        lag.insert(lag.end(), zs.begin() + (size_t)c * n_sets, zs.begin() + (size_t)(c + 1) * n_sets);
+        lag.insert(lag.end(), lzs.begin() + (size_t)c * L, lzs.begin() + (size_t)(c + 1) * L);
+        for (uint32_t l = 0; l < L; l++) { lag.push_back(pin[(size_t)c * L + l]); lag.push_back(ptab[(size_t)c * L + l]); }
+    }
+    if (side) for (void* p : lag) side_ext.push_back(ext_of.at(p));
     if (!side) PK(zk_lagrange_to_coeff_batch_dev(ctx, lag.data(), lag.size(), k));
     void* h_ext = by_cosets ? nullptr : mem.get(en * 32);
     if (!by_cosets && !h_ext) return ZK_ERR_HIP;
@@ -819,41 +857,46 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
         if (!blk) return ZK_ERR_HIP;
         for (uint32_t j = 0; j < low_cosets; j++) numer_low[j] = (char*)blk + (size_t)j * col_bytes;
     }
+    // halo2's fold across circuits (evaluate_h keeps `values` from one circuit to the next): circuit 0 writes the numerator, every later circuit c runs in accumulate
+    // mode, out <- out * y^E + N_c, so the output ends as sum_c y^(E (m - 1 - c)) N_c — in the same launches, one read of out more each
     if (by_cosets) {
-        std::vector<void*> cols(lag.size());
+        std::vector<void*> cols(W);                                   // (circuit c's coset columns reuse circuit c - 1's buffers)
         for (auto& e : cols) { e = mem.get(col_bytes); if (!e) return ZK_ERR_HIP; }
         for (auto& e : numer) { e = mem.get(col_bytes); if (!e) return ZK_ERR_HIP; }
         for (uint32_t j = 0; j < n_pieces; j++) {
-            PK(zk_coeff_to_coset_batch_dev(ctx, (const void* const*)lag.data(), cols.data(), cols.size(), k, ek, j));
-            std::vector<const void*> e_in, e_tab;
-            zk_quotient_args a;
-            quotient_args(a, cols.data(), e_in, e_tab);
-            a.fixed = pk->coset_fixed + (size_t)j * pk->n_fixed; a.perm_cosets = pk->coset_sigma + (size_t)j * pk->n_perm_columns;
-            a.l0 = pk->coset_l[3 * j]; a.l_last = pk->coset_l[3 * j + 1]; a.l_active_row = pk->coset_l[3 * j + 2];
-            a.out = numer[j];
-            if (!low_cosets) PK(zk_quotient_run_coset_dev(ctx, pk->program, &a, j));
-            else {
-                PK(zk_quotient_run_coset_part_dev(ctx, pk->program, &a, j, 1));
-                if (j < low_cosets) { a.out = numer_low[j]; PK(zk_quotient_run_coset_part_dev(ctx, pk->program, &a, j, 2)); }
+            for (uint32_t c = 0; c < m; c++) {
+                PK(zk_coeff_to_coset_batch_dev(ctx, (const void* const*)lag.data() + (size_t)c * W, cols.data(), cols.size(), k, ek, j));
+                std::vector<const void*> e_in, e_tab;
+                zk_quotient_args a;
+                quotient_args(a, cols.data(), e_in, e_tab);
+                a.fixed = pk->coset_fixed + (size_t)j * pk->n_fixed; a.perm_cosets = pk->coset_sigma + (size_t)j * pk->n_perm_columns;
+                a.l0 = pk->coset_l[3 * j]; a.l_last = pk->coset_l[3 * j + 1]; a.l_active_row = pk->coset_l[3 * j + 2];
+                a.out = numer[j];
+                if (!low_cosets) PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, j, 0) : zk_quotient_run_coset_dev(ctx, pk->program, &a, j));
+                else {
+                    PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, j, 1) : zk_quotient_run_coset_part_dev(ctx, pk->program, &a, j, 1));
+                    if (j < low_cosets) { a.out = numer_low[j]; PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, j, 2) : zk_quotient_run_coset_part_dev(ctx, pk->program, &a, j, 2)); }
+                }
             }
         }
         for (auto e : cols) mem.give_back(e);
     } else if (!sharded) {
-        std::vector<void*> ext(lag.size());
+        std::vector<void*> ext(side ? lag.size() : W);               // side lane: every circuit's extended columns exist already; otherwise one circuit's at a time
         if (side) ext = side_ext;
-        else {
-            for (auto& e : ext) { e = mem.get(en * 32); if (!e) return ZK_ERR_HIP; }
-            PK(zk_coeff_to_extended_batch_dev(ctx, (const void* const*)lag.data(), ext.data(), ext.size(), k, ek));
-        }
-        std::vector<const void*> e_in, e_tab;
-        zk_quotient_args a;
-        quotient_args(a, ext.data(), e_in, e_tab);
-        a.fixed = pk->fixed_cosets; a.l0 = pk->l0; a.l_last = pk->l_last; a.l_active_row = pk->l_active_row; a.perm_cosets = pk->sigma_cosets; a.out = h_ext;
-        if (!low_cosets) PK(zk_quotient_run_dev(ctx, pk->program, &a));
-        else {
-            PK(zk_quotient_run_high_dev(ctx, pk->program, &a));
-            a.out = numer_low[0];
-            PK(zk_quotient_run_low_dev(ctx, pk->program, &a, low_cosets));
+        else for (auto& e : ext) { e = mem.get(en * 32); if (!e) return ZK_ERR_HIP; }
+        for (uint32_t c = 0; c < m; c++) {
+            void* const* ec = ext.data() + (side ? (size_t)c * W : 0);
+            if (!side) PK(zk_coeff_to_extended_batch_dev(ctx, (const void* const*)lag.data() + (size_t)c * W, ext.data(), W, k, ek));
+            std::vector<const void*> e_in, e_tab;
+            zk_quotient_args a;
+            quotient_args(a, ec, e_in, e_tab);
+            a.fixed = pk->fixed_cosets; a.l0 = pk->l0; a.l_last = pk->l_last; a.l_active_row = pk->l_active_row; a.perm_cosets = pk->sigma_cosets; a.out = h_ext;
+            if (!low_cosets) PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, UINT32_MAX, 0) : zk_quotient_run_dev(ctx, pk->program, &a));
+            else {
+                PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, UINT32_MAX, 1) : zk_quotient_run_high_dev(ctx, pk->program, &a));
+                a.out = numer_low[0];
+                PK(c ? zk_quotient_run_acc_dev(ctx, pk->program, &a, UINT32_MAX, 2) : zk_quotient_run_low_dev(ctx, pk->program, &a, low_cosets));
+            }
         }
         for (auto e : ext) mem.give_back(e);
     } else {
@@ -930,20 +973,22 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
         PK(zk_fr_lincomb_dev(ctx, (const void* const*)pieces.data(), sc.data(), n_pieces, n, h_poly));
     }
     const Fe x_last = rot(-(int32_t)(bf + 1)), x_next = rot(1), x_prev = rot(-1);
-    std::vector<Query> q;
-    for (uint32_t i = 0; i < pk->n_advice_queries; i++) q.push_back({adv[pk->advice_queries[2 * i]], rot((int32_t)pk->advice_queries[2 * i + 1]), Fr::zero()});
+    std::vector<Query> q;                                             // in the transcript's order: advice (per circuit), fixed, random, sigma, permutation (per circuit), lookups (per circuit)
+    for (uint32_t c = 0; c < m; c++)
+        for (uint32_t i = 0; i < pk->n_advice_queries; i++) q.push_back({adv[(size_t)c * A + pk->advice_queries[2 * i]], rot((int32_t)pk->advice_queries[2 * i + 1]), Fr::zero()});
     for (uint32_t i = 0; i < pk->n_fixed_queries; i++) q.push_back({pk->fixed_polys[pk->fixed_queries[2 * i]], rot((int32_t)pk->fixed_queries[2 * i + 1]), Fr::zero()});
     q.push_back({random_poly, x, Fr::zero()});
     for (uint32_t j = 0; j < pk->n_perm_columns; j++) q.push_back({pk->sigma_polys[j], x, Fr::zero()});
-    for (uint32_t s = 0; s < n_sets; s++) {
-        q.push_back({zs[s], x, Fr::zero()});
-        q.push_back({zs[s], x_next, Fr::zero()});
-        if (s + 1 < n_sets) q.push_back({zs[s], x_last, Fr::zero()});
+    for (size_t cs = 0; cs < mS; cs++) {
+        const uint32_t s = (uint32_t)(cs % n_sets);
+        q.push_back({zs[cs], x, Fr::zero()});
+        q.push_back({zs[cs], x_next, Fr::zero()});
+        if (s + 1 < n_sets) q.push_back({zs[cs], x_last, Fr::zero()});
     }
-    for (uint32_t l = 0; l < L; l++) {
-        q.push_back({lzs[l], x, Fr::zero()}); q.push_back({lzs[l], x_next, Fr::zero()});
-        q.push_back({pin[l], x, Fr::zero()}); q.push_back({pin[l], x_prev, Fr::zero()});
-        q.push_back({ptab[l], x, Fr::zero()});
+    for (size_t cl = 0; cl < mL; cl++) {
+        q.push_back({lzs[cl], x, Fr::zero()}); q.push_back({lzs[cl], x_next, Fr::zero()});
+        q.push_back({pin[cl], x, Fr::zero()}); q.push_back({pin[cl], x_prev, Fr::zero()});
+        q.push_back({ptab[cl], x, Fr::zero()});
     }
     q.push_back({h_poly, x, Fr::zero()});
     {
@@ -956,26 +1001,32 @@ static int create_proof_body(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const void
     }
     clk.lap(7);
     // ---- 9. ProverSHPLONK: queries in the multi-open order ---------------------------------------------------------------------------------------------------------------
+    // halo2's query list: per circuit its advice, permutation and lookup queries; then fixed, sigma and the vanishing argument once (queries of different circuits are
+    // distinct polynomials at the same points)
     std::vector<Query> mq;
     {
         size_t it = 0;
-        std::vector<Query> q_adv(q.begin(), q.begin() + pk->n_advice_queries); it += pk->n_advice_queries;
+        std::vector<std::vector<Query>> q_adv(m);
+        for (uint32_t c = 0; c < m; c++) { q_adv[c].assign(q.begin() + it, q.begin() + it + pk->n_advice_queries); it += pk->n_advice_queries; }
         std::vector<Query> q_fix(q.begin() + it, q.begin() + it + pk->n_fixed_queries); it += pk->n_fixed_queries;
         const Query q_rand = q[it++];
         std::vector<Query> q_sig(q.begin() + it, q.begin() + it + pk->n_perm_columns); it += pk->n_perm_columns;
-        std::vector<Query> q_pa, q_pl;
-        for (uint32_t s = 0; s < n_sets; s++) { q_pa.push_back(q[it++]); q_pa.push_back(q[it++]); if (s + 1 < n_sets) q_pl.push_back(q[it++]); }
-        std::vector<Query> q_lk;
-        for (uint32_t l = 0; l < L; l++) {
-            const Query pz = q[it], pzn = q[it + 1], pa = q[it + 2], pai = q[it + 3], ps = q[it + 4];
-            it += 5;
-            q_lk.push_back(pz); q_lk.push_back(pa); q_lk.push_back(ps); q_lk.push_back(pai); q_lk.push_back(pzn);      // lookup::Evaluated::open order
-        }
+        std::vector<std::vector<Query>> q_pa(m), q_pl(m), q_lk(m);
+        for (uint32_t c = 0; c < m; c++)
+            for (uint32_t s = 0; s < n_sets; s++) { q_pa[c].push_back(q[it++]); q_pa[c].push_back(q[it++]); if (s + 1 < n_sets) q_pl[c].push_back(q[it++]); }
+        for (uint32_t c = 0; c < m; c++)
+            for (uint32_t l = 0; l < L; l++) {
+                const Query pz = q[it], pzn = q[it + 1], pa = q[it + 2], pai = q[it + 3], ps = q[it + 4];
+                it += 5;
+                q_lk[c].push_back(pz); q_lk[c].push_back(pa); q_lk[c].push_back(ps); q_lk[c].push_back(pai); q_lk[c].push_back(pzn);      // lookup::Evaluated::open order
+            }
         const Query q_h = q[it++];
-        mq = q_adv;
-        mq.insert(mq.end(), q_pa.begin(), q_pa.end());
-        mq.insert(mq.end(), q_pl.rbegin(), q_pl.rend());
-        mq.insert(mq.end(), q_lk.begin(), q_lk.end());
+        for (uint32_t c = 0; c < m; c++) {
+            mq.insert(mq.end(), q_adv[c].begin(), q_adv[c].end());
+            mq.insert(mq.end(), q_pa[c].begin(), q_pa[c].end());
+            mq.insert(mq.end(), q_pl[c].rbegin(), q_pl[c].rend());
+            mq.insert(mq.end(), q_lk[c].begin(), q_lk[c].end());
+        }
         mq.insert(mq.end(), q_fix.begin(), q_fix.end());
         mq.insert(mq.end(), q_sig.begin(), q_sig.end());
         mq.push_back(q_h); mq.push_back(q_rand);
@@ -1364,6 +1415,21 @@ extern "C" int zk_plonk_prove(zk_ctx* ctx, uint64_t pk, const void* const* advic
     }
     struct Done { zk_ctx* ctx; PkHandle* h; ~Done() { std::lock_guard<std::mutex> lk(g_pk_mu); if (--h->in_use == 0 && h->released) pk_drop(ctx, h); } } done{ctx, h};
     return zk_plonk_create_proof(ctx, &h->desc, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
+                                    const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+    if (!ctx) return ZK_ERR_ARG;
+    PkHandle* h = nullptr;
+    {   // (as zk_plonk_prove)
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        auto it = g_pk_handles.find({ctx, pk});
+        if (it == g_pk_handles.end()) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_multi: unknown key %llu", (unsigned long long)pk);
+        h = it->second;
+        h->in_use++;
+    }
+    struct Done { zk_ctx* ctx; PkHandle* h; ~Done() { std::lock_guard<std::mutex> lk(g_pk_mu); if (--h->in_use == 0 && h->released) pk_drop(ctx, h); } } done{ctx, h};
+    return zk_plonk_create_proof_multi(ctx, &h->desc, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
 } ZK_ABI_CATCH(ctx)
 
 // zk_ctx_destroy (capi.hip): the keys this context still holds go with it (before its programs are released)

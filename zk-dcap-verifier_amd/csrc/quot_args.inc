@@ -17,4 +17,8 @@ struct QuotArgs {
     void* out;
     void* state;                   // generated kernels only: the slots that are live between two kernels of a program, plane s at state + s * state_stride (32 bytes per row)
     unsigned long long state_stride;
+    // accumulate mode (zk_quotient_run_acc_dev): out holds halo2's PreviousValue on entry and receives out * consts[acc_const] + numerator, consts[acc_const] = y^E
+    // (E = the identities of the whole program).  The generated kernels then carry their running value in acc_state instead of out.
+    uint32_t accumulate, acc_const;
+    void* acc_state;
 };

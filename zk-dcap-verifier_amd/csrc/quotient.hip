@@ -128,6 +128,7 @@ ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) ZK_WAVES_PER_EU(4) quotient_kernel(QuotArgs
         }
         ins = nxt; pa = na; pb = nb; pc_ = nc;
     }
+    if (q.accumulate) acc = Fr::red2p(Fr::add_lazy(Fr::mul_lazy(load_u256(q.out, oidx), load_u256(q.consts, q.acc_const)), acc));      // previous * y^E + this numerator
     store_u256(q.out, oidx, Fr::normalize(acc));
 }
 
@@ -906,7 +907,7 @@ int quotient_set_lds_attr() {
 // part: 0 = every identity; 1 / 2 = the high / low part of a program that has a degree split (QuotProgram::part_hi / part_lo).  low_cosets > 0 (part 2, coset < 0): the
 // columns are the whole extended domain but only the rows of its cosets 0 .. low_cosets-1 are evaluated — thread i of coset j reads row i * 2^(ek-k) + j — and
 // out receives low_cosets x n values, coset-major (what zk_cosets_to_pieces_dev takes).
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets) {
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate) {
     auto it = ctx->programs.find(prog);
     if (it == ctx->programs.end()) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: unknown program %llu", (unsigned long long)prog);
     if (part && (!it->second->part_hi || !it->second->part_lo)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_part_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
@@ -934,7 +935,7 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
     for (auto p : cols) if (!p) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: null column pointer");
     // constants of this run
     auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    std::vector<u256> consts(P.n_consts);
+    std::vector<u256> consts(P.n_consts + (accumulate ? 1 : 0));            // (accumulate mode: y^E last)
     for (size_t i = 0; i < P.graph_consts.size(); i++) consts[i] = P.graph_consts[i];
     consts[P.c_zero] = Fr::zero(); consts[P.c_one] = Fr::one();
     for (uint32_t i = 0; i < P.n_challenges; i++) consts[P.c_chal + i] = rd((const char*)a->challenges + 32 * i);
@@ -944,6 +945,11 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
         u256 acc = Fr::one(), base = consts[P.c_y];
         for (uint32_t e = P.ypow_exps[i]; e; e >>= 1) { if (e & 1) acc = Fr::mul(acc, base); base = Fr::sqr(base); }
         consts[P.c_ypow + i] = acc;
+    }
+    if (accumulate) {                                                 // E = every identity of the WHOLE program, also for a degree part: high + low still sum to previous * y^E + numerator
+        u256 acc = Fr::one(), base = consts[P.c_y];
+        for (uint32_t e = it->second->folds_taken; e; e >>= 1) { if (e & 1) acc = Fr::mul(acc, base); base = Fr::sqr(base); }
+        consts[P.n_consts] = acc;
     }
     {   // delta_j = beta * ZETA * DELTA^j  (current_delta of evaluate_h without the omega^idx factor)
         const uint64_t zl[4] = BN254_FR_ZETA_M, dl[4] = BN254_FR_DELTA_M;
@@ -965,7 +971,7 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
     }
     hipStream_t st = ctx->stream;
     // the run's constants | column pointers | rotation offsets, in this context's own buffer
-    const size_t off_cols = ((size_t)P.n_consts * 32 + 32 + 255) & ~(size_t)255, off_rot = (off_cols + (size_t)P.n_cols * sizeof(void*) + 8 + 255) & ~(size_t)255;
+    const size_t off_cols = ((size_t)consts.size() * 32 + 32 + 255) & ~(size_t)255, off_rot = (off_cols + (size_t)P.n_cols * sizeof(void*) + 8 + 255) & ~(size_t)255;
     ZK_HIP(ctx->ws_quot.ensure(off_rot + (P.rotations.size() + 1) * 4));
     void* const d_consts = ctx->ws_quot.p;
     void* const d_cols = (char*)ctx->ws_quot.p + off_cols;
@@ -978,6 +984,7 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
     q.code = (const uint4*)P.d_code; q.n_instr = (uint32_t)P.code.size(); q.consts = d_consts;
     q.cols = (const void* const*)d_cols; q.rot_off = (const uint32_t*)d_rot; q.size_log = size_log; q.out = a->out;
     q.uses_xpow = P.uses_xpow ? 1 : 0;
+    q.accumulate = accumulate ? 1u : 0u; q.acc_const = P.n_consts;
     q.xpow_mul = cm ? 1u << (P.ek - P.k) : 1u;
     q.xpow_add = cm ? (uint32_t)coset : 0u;
     if (P.uses_xpow) {
@@ -1169,7 +1176,7 @@ int evaluate_h_host(zk_ctx* ctx, uint64_t pkh, const void* const* advice, const 
     qa.lookup_product = dyn + P.n_advice + P.n_instance + P.n_sets;
     qa.lookup_input = qa.lookup_product + P.n_lookups; qa.lookup_table = qa.lookup_input + P.n_lookups;
     qa.challenges = challenges; qa.beta = beta; qa.gamma = gamma; qa.theta = theta; qa.y = y; qa.out = pk->h_ext;
-    int rc = quotient_run(ctx, pk->prog, &qa, -1, 0, 0, 0, 0);
+    int rc = quotient_run(ctx, pk->prog, &qa, -1, 0, 0, 0, 0, 0);
     if (rc) return rc;
     size_t out_bytes = (size_t)32 << P.ek;
     if (finish) {

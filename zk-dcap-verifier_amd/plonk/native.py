@@ -161,9 +161,29 @@ class NativeProver:
         self.proof_cap = (64 if transcript == "evm" else 32) * (cs.num_advice_columns + 3 * len(cs.lookups) + len(cs.permutation_columns) + 16 +
                                len(aq) + len(fq) + 1 + len(cs.permutation_columns) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups) + 8)
 
+    def proof_cap_for(self, n_circuits: int) -> int:
+        """an upper bound of the proof bytes of one proof over n_circuits circuits (the per-circuit commitments and evaluations n_circuits times)"""
+        cs = self.pk.vk.cs
+        unit = 64 if self.desc.transcript == 2 else 32
+        per_circuit = cs.num_advice_columns + 3 * len(cs.lookups) + len(cs.permutation_columns) + len(cs.advice_queries()) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups)
+        return self.proof_cap + unit * (n_circuits - 1) * per_circuit
+
     def create_proof(self, advice: Sequence, instances: Sequence[Sequence[int]], rng) -> bytes:
         """advice: host (n, 4) uint64 arrays (page-locked or ordinary) or device buffers — all of one kind; instances: canonical ints per instance column;
         rng: numpy Generator (seeded) or fields.OsRng().  Returns the proof bytes."""
+        return self._prove(0, list(advice), list(instances), rng, self.proof_cap)
+
+    def create_proof_multi(self, advices: Sequence[Sequence], instances_list: Sequence[Sequence[Sequence[int]]], rng, proof_cap: int | None = None) -> bytes:
+        """halo2's create_proof over a slice of circuits: ONE proof over len(advices) circuits that share this key (zk_plonk_create_proof_multi).  advices[c] and
+        instances_list[c] are circuit c's, as create_proof takes them; one circuit gives create_proof's bytes.  proof_cap: the output buffer (default: large enough)."""
+        m = len(advices)
+        assert m == len(instances_list), "one instance list per circuit"
+        adv = [a for per in advices for a in per]
+        inst = [col for per in instances_list for col in per]
+        return self._prove(m, adv, inst, rng, self.proof_cap_for(max(m, 1)) if proof_cap is None else proof_cap)
+
+    def _prove(self, m: int, advice: list, instances: list, rng, cap: int) -> bytes:
+        """m = 0: zk_plonk_create_proof; m >= 1: zk_plonk_create_proof_multi over m circuits"""
         be, d = self.be, self.desc
         on_device = not isinstance(advice[0], np.ndarray) if len(advice) else False
         keep = [np.ascontiguousarray(a, dtype=np.uint64) for a in advice] if not on_device else []
@@ -180,10 +200,14 @@ class NativeProver:
             except BaseException as e:                                  # never let an exception cross the FFI
                 errors.append(e)
         cb = RNG_FN(draw)
-        out = np.empty(self.proof_cap, dtype=np.uint8)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
         ln = C.c_size_t()
-        rc = be.lib.zk_plonk_create_proof(be.ctx, C.byref(d), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
-                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(ln))
+        if m == 0:
+            rc = be.lib.zk_plonk_create_proof(be.ctx, C.byref(d), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
+                                              out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
+        else:
+            rc = be.lib.zk_plonk_create_proof_multi(be.ctx, C.byref(d), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
+                                                    out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
         if errors:
             raise errors[0]
         if getattr(self, "comm_errors", None):

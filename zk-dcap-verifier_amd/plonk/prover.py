@@ -14,7 +14,8 @@ Every O(n) step runs on the GPU through the product API and stays resident in HB
     evaluations            zk_eval_polynomial_batch_dev
     SHPLONK                zk_fr_lincomb_dev, zk_kate_division_dev
 The host does what it does in the reference: Fiat-Shamir hashing, point encoding, O(#columns) bookkeeping.
-Single circuit instance per proof (the reference passes `&[circuit]`); no user challenges / multi-phase advice.
+Single circuit instance per proof (the reference passes `&[circuit]`); no user challenges / multi-phase advice.  This readable twin stays single-circuit:
+one proof over several circuits is the native path's alone (NativeProver.create_proof_multi, zk_plonk_create_proof_multi).
 """
 from __future__ import annotations
 
