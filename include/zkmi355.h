@@ -52,9 +52,10 @@ typedef struct zk_ctx zk_ctx;
  * call instead of handing the library bytes past the end of its object.  Fields are only ever APPENDED, and each append bumps ZK_ABI_VERSION; a binding
  * asserts at start-up that zk_abi_version() is the ZK_ABI_VERSION it was written against and that zk_abi_struct_size(name) equals its own size of every
  * struct it declares (shim/halo2_proofs_mi355x/src/mi355x.rs does; tests/test_shim_abi.py diffs the declarations field by field). */
-#define ZK_ABI_VERSION 4u
+#define ZK_ABI_VERSION 5u
 uint32_t zk_abi_version(void);
-/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host") in this build of the library; 0 for an unknown name */
+/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure") in this build of the library; 0 for an
+ * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify). */
 uint32_t zk_abi_struct_size(const char* struct_name);
 #define ZK_STRUCT_INIT(s) do { memset(&(s), 0, sizeof(s)); (s).struct_size = (uint32_t)sizeof(s); } while (0)   /* needs <string.h> */
 
@@ -465,6 +466,44 @@ int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const vo
 int zk_plonk_last_phase_ms(double out[9]);
 /* return the per-proof device buffers zk_plonk_create_proof keeps for reuse on this context (zk_ctx_destroy does it too) */
 int zk_plonk_trim(zk_ctx* ctx);
+
+/* ---- MockProver: halo2_proofs::dev::MockProver::verify on the device ------------------------------------------------------------------------------------ *
+ * The witness check the reference runs before it proves (MockProver::run(k, &circuit, vec![]).assert_satisfied(), circuits/src/sgx_dcap_verifier.rs:790-794), for
+ * single-phase circuits without challenges, with the semantics of zk-dcap-verifier_amd/plonk/dev.py's MockProver.verify (u = 2^k - blinding_factors - 1):
+ *   gates    every polynomial of cs.gates on rows 0 .. u-1, rotations taken mod 2^k;
+ *   lookups  for every lookup and every input row r < u: the input tuple occurs among the table tuples of rows < u;
+ *   copies   for every permutation column j and every row of 2^k: the value of (j, row) equals the value of map(j, row), both fully reduced.
+ * Records: gate failures first, sorted by (row, index); then lookup failures by (index, row); then copy failures by (index, row).  counts[3] receives the exact
+ * number of failures of each kind, out the first `cap` records (out may be NULL when cap = 0), *n_written = min(cap, total).  Detection folds with random scalars
+ * the library draws per call (r over the gate polynomials, theta over a lookup tuple's expressions): a failing row goes unseen with probability at most E / |Fr|
+ * (E gate polynomials), a missing tuple of m expressions at most (m - 1) / |Fr|; which polynomial of a failing row failed is decided exactly.
+ * ZK_ERR_ARG: a wrong struct_size, NULL columns, a blob for another k or other column counts, a non-canonical instance, a mapping entry out of range;
+ * ZK_ERR_PROGRAM: a blob that declares challenges (n_challenges > 0: the native prover does not model them either).
+ * zk_mock_failure is an output record and carries no struct_size; both structs are sized by zk_abi_struct_size. */
+typedef struct zk_mock_desc zk_mock_desc;
+typedef struct zk_mock_failure zk_mock_failure;
+struct zk_mock_desc {
+    uint32_t struct_size;                       /* sizeof(zk_mock_desc) of the caller (ABI versioning) */
+    uint32_t k, blinding_factors;               /* usable rows u = 2^k - blinding_factors - 1 (ConstraintSystem::blinding_factors) */
+    uint32_t n_fixed, n_advice, n_instance, n_lookups, n_perm_columns;
+    const uint32_t* perm_columns;               /* n_perm_columns x (column_type, index), as zk_plonk_pk_host */
+    const void* evaluator_zkq1; size_t evaluator_zkq1_len;                      /* the SAME blob zk_plonk_pk_build takes; only its custom gates are used */
+    const void* const* lookup_input_zkq1; const size_t* lookup_input_zkq1_len;   /* the same per-lookup programs as zk_plonk_pk_host */
+    const void* const* lookup_table_zkq1; const size_t* lookup_table_zkq1_len;
+    const void* const* fixed_values;            /* n_fixed columns, 2^k x 32 B Montgomery; HOST, or DEVICE with values_on_device */
+    const void* const* advice_values;           /* n_advice columns, same */
+    const void* const* instances; const uint32_t* instance_lens;   /* HOST canonical 32 B values, zero-padded to 2^k (as zk_plonk_create_proof) */
+    const uint32_t* perm_map_column;            /* n_perm_columns x 2^k, HOST: the copy-constraint mapping (halo2's permutation::keygen::Assembly::mapping), */
+    const uint32_t* perm_map_row;               /*   column = index into perm_columns */
+    uint32_t values_on_device;
+};
+struct zk_mock_failure {
+    uint32_t kind;                              /* 0 gate, 1 lookup, 2 copy */
+    uint32_t index;                             /* gate: polynomial index in cs.gates order (halo2's gates' polynomials flattened); lookup: lookup index; copy: index into perm_columns */
+    uint32_t row;
+    uint32_t other_column, other_row;           /* copy only: the mapped cell (perm_columns index, row) */
+};
+int zk_mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* desc, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written);
 
 /* library / build identification */
 const char* zk_version(void);

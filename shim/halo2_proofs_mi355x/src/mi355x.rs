@@ -17,7 +17,7 @@ pub struct ZkCtx {
 }
 
 /// ZK_ABI_VERSION of the include/zkmi355.h this file was written against
-pub const ZK_ABI_VERSION: u32 = 4;
+pub const ZK_ABI_VERSION: u32 = 5;
 
 /// field-for-field `zk_quotient_args`
 #[repr(C)]

@@ -26,7 +26,7 @@ class ZkError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 4          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
+ABI_VERSION = 5          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
 
 
 class QuotientArgs(C.Structure):
@@ -37,6 +37,25 @@ class QuotientArgs(C.Structure):
                 ("lookup_product", C.c_void_p), ("lookup_input", C.c_void_p), ("lookup_table", C.c_void_p),
                 ("challenges", C.c_void_p), ("beta", C.c_void_p), ("gamma", C.c_void_p), ("theta", C.c_void_p),
                 ("y", C.c_void_p), ("out", C.c_void_p)]
+
+
+class MockDesc(C.Structure):
+    """zk_mock_desc (zk_mock_prover_verify)"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("blinding_factors", C.c_uint32),
+                ("n_fixed", C.c_uint32), ("n_advice", C.c_uint32), ("n_instance", C.c_uint32), ("n_lookups", C.c_uint32), ("n_perm_columns", C.c_uint32),
+                ("perm_columns", C.c_void_p),
+                ("evaluator_zkq1", C.c_void_p), ("evaluator_zkq1_len", C.c_size_t),
+                ("lookup_input_zkq1", C.c_void_p), ("lookup_input_zkq1_len", C.c_void_p),
+                ("lookup_table_zkq1", C.c_void_p), ("lookup_table_zkq1_len", C.c_void_p),
+                ("fixed_values", C.c_void_p), ("advice_values", C.c_void_p),
+                ("instances", C.c_void_p), ("instance_lens", C.c_void_p),
+                ("perm_map_column", C.c_void_p), ("perm_map_row", C.c_void_p),
+                ("values_on_device", C.c_uint32)]
+
+
+class MockFailure(C.Structure):
+    """zk_mock_failure: kind 0 gate / 1 lookup / 2 copy"""
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("other_column", C.c_uint32), ("other_row", C.c_uint32)]
 
 
 def _load(path: str):
@@ -55,6 +74,9 @@ def _load(path: str):
         raise RuntimeError(f"{path}: ABI version {lib.zk_abi_version()}, this binding is written against {ABI_VERSION} (rebuild: __graft_entry__.build())")
     if lib.zk_abi_struct_size(b"zk_quotient_args") != C.sizeof(QuotientArgs):
         raise RuntimeError(f"{path}: sizeof(zk_quotient_args) = {lib.zk_abi_struct_size(b'zk_quotient_args')}, the binding's QuotientArgs has {C.sizeof(QuotientArgs)}")
+    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure)):
+        if lib.zk_abi_struct_size(name) != C.sizeof(st):
+            raise RuntimeError(f"{path}: sizeof({name.decode()}) = {lib.zk_abi_struct_size(name)}, the binding's {st.__name__} has {C.sizeof(st)}")
     return lib
 
 
@@ -467,6 +489,61 @@ class Backend:
         assert sc.shape[0] == len(polys)
         self._ck(self.lib.zk_fr_lincomb_dev(self.ctx, self._ptr_array(polys), sc.ctypes.data_as(C.c_void_p), C.c_size_t(len(polys)), C.c_size_t(n),
                                             C.c_void_p(_dptr(out_dev))))
+
+    # -- MockProver ------------------------------------------------------------------------------
+    def mock_prover_verify(self, *, k: int, blinding_factors: int, n_fixed: int, n_advice: int, n_instance: int, perm_columns, evaluator_blob: bytes,
+                           lookup_input_blobs, lookup_table_blobs, fixed, advice, instances, perm_map_column=None, perm_map_row=None, cap: int = 0,
+                           struct_size: int | None = None):
+        """zk_mock_prover_verify.  fixed / advice: (2^k, 4) uint64 Montgomery arrays (host) or device buffers (all of one kind; None = a NULL column);
+        instances: canonical ints per instance column; perm_map_column / perm_map_row: (n_perm_columns, 2^k) integer arrays (Assembly.map_c / map_r).
+        Returns ([(kind, index, row, other_column, other_row)] for the first `cap` failures, (gate, lookup, copy) counts)."""
+        keep = []
+
+        def arr(a, dtype):
+            a = np.ascontiguousarray(np.asarray(a).astype(dtype, copy=False))
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        def ptrs(vals):
+            p = (C.c_void_p * max(1, len(vals)))(*vals)
+            keep.append(p)
+            return C.cast(p, C.c_void_p).value
+        cols = list(fixed) + list(advice)
+        on_device = any(c is not None and not isinstance(c, np.ndarray) for c in cols)
+        if on_device:
+            col_ptr = lambda c: None if c is None else _dptr(c)
+        else:
+            col_ptr = lambda c: None if c is None else arr(c, np.uint64)
+        blob_bufs = [evaluator_blob] + list(lookup_input_blobs) + list(lookup_table_blobs)
+        bufs = [(C.c_char * max(1, len(b))).from_buffer_copy(b or b"\0") for b in blob_bufs]
+        keep.extend(bufs)
+        L = len(lookup_input_blobs)
+        inst = [np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in col) or bytes(32), dtype=np.uint8).copy() for col in instances]
+        keep.extend(inst)
+        d = MockDesc()
+        d.struct_size = C.sizeof(MockDesc) if struct_size is None else struct_size
+        d.k, d.blinding_factors = k, blinding_factors
+        d.n_fixed, d.n_advice, d.n_instance, d.n_lookups, d.n_perm_columns = n_fixed, n_advice, n_instance, L, len(perm_columns)
+        d.perm_columns = arr([v for t, i in perm_columns for v in (t, i)], np.uint32) if perm_columns else None
+        d.evaluator_zkq1, d.evaluator_zkq1_len = C.addressof(bufs[0]), len(evaluator_blob)
+        d.lookup_input_zkq1 = ptrs([C.addressof(b) for b in bufs[1:1 + L]])
+        d.lookup_input_zkq1_len = arr([len(b) for b in lookup_input_blobs] or [0], np.uint64)
+        d.lookup_table_zkq1 = ptrs([C.addressof(b) for b in bufs[1 + L:]])
+        d.lookup_table_zkq1_len = arr([len(b) for b in lookup_table_blobs] or [0], np.uint64)
+        d.fixed_values = ptrs([col_ptr(c) for c in fixed])
+        d.advice_values = ptrs([col_ptr(c) for c in advice])
+        d.instances = ptrs([a.ctypes.data for a in inst])
+        d.instance_lens = arr([len(col) for col in instances] or [0], np.uint32)
+        if perm_columns:
+            d.perm_map_column = arr(perm_map_column, np.uint32)
+            d.perm_map_row = arr(perm_map_row, np.uint32)
+        d.values_on_device = 1 if on_device else 0
+        out = (MockFailure * max(1, cap))()
+        counts = (C.c_uint64 * 3)()
+        written = C.c_size_t()
+        self._ck(self.lib.zk_mock_prover_verify(self.ctx, C.byref(d), out, C.c_size_t(cap), counts, C.byref(written)))
+        recs = [(f.kind, f.index, f.row, f.other_column, f.other_row) for f in out[: written.value]]
+        return recs, (int(counts[0]), int(counts[1]), int(counts[2]))
 
     # -- quotient -------------------------------------------------------------------------------
     def quotient_program_load(self, blob: bytes) -> int:

@@ -1,0 +1,476 @@
+// MockProver::verify on the device — halo2_proofs src/dev.rs, the witness check the reference runs before it proves
+// (`MockProver::run(k, &circuit, vec![]).unwrap().assert_satisfied()`, circuits/src/sgx_dcap_verifier.rs:790-794).  The specification is
+// zk-dcap-verifier_amd/plonk/dev.py's MockProver.verify: the same failures, in the same order (include/zkmi355.h, zk_mock_prover_verify).
+//
+// Four passes over the rows, each a HIP kernel:
+//   1. gates, detection: the Evaluator blob's custom gates alone, compiled at extended_k = k (quotient_program_load_gates), fold every gate polynomial of a row
+//      in a random r — Horner, as evaluate_h folds them in y — on the existing interpreter; rows < u whose value is non-zero are compacted into an ascending list.
+//      A failing row folds to zero only if r is a root of the non-zero polynomial sum_i g_i(row) X^(E-1-i): probability at most (E - 1) / |Fr| <= E / |Fr| per
+//      row, E = the number of gate polynomials.
+//   2. gates, attribution: the same program on the listed rows only, one bit per polynomial (quotient_run's row-list mode; the zero test runs on each fully
+//      reduced value, so it is exact) — failing rows x polynomials of work, whatever 2^k is, and exact counts when every row fails.
+//   3. lookups: input and table tuples theta-compressed by the blobs' own expression programs (as the prover compresses them), theta random; the rows < u of
+//      every distinct table blob sorted (bitonic network, full 256-bit order), every input row < u binary-searched, misses compacted.  Two different tuples of m
+//      expressions compress to the same value with probability at most (m - 1) / |Fr| — the bound halo2's lookup argument itself rests on.
+//   4. copies: one gather-compare over the n_perm_columns x 2^k copy mapping (values fully reduced), mismatches compacted.
+// Compaction (mp_compact): a 64-bit __ballot per wave and its popcount, a count per workgroup, one scan over the workgroups and a scatter — positions follow the
+// element order, no arrival-order atomics, so every list is deterministic.  The records and the counts are assembled on the host from the lists.
+#include "ctx.h"
+#include "quotient.h"
+#include <algorithm>
+#include <list>
+#include <random>
+#include <string>
+
+namespace zk {
+int quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog);
+int quotient_program_release(zk_ctx* ctx, uint64_t prog);
+
+namespace {
+constexpr uint32_t MP_T = 256, MP_E = 8, MP_TILE = MP_T * MP_E, MP_WAVES = MP_T / 64;   // compaction: a workgroup owns MP_TILE consecutive flags
+constexpr uint32_t MP_LOCAL = 2 * MP_T;                                                  // bitonic steps in LDS: values per workgroup
+
+// 64-bit ballot of the calling lane's wave (gfx950: wave64).  The emulator has no waves: there the same mask is assembled through LDS.
+__device__ inline uint64_t mp_ballot(bool p, uint32_t* lds) {
+#ifdef ZK_EMU
+    const uint32_t tid = threadIdx.x;
+    lds[tid] = p ? 1u : 0u;
+    __syncthreads();
+    uint64_t m = 0;
+    for (uint32_t l = 0; l < 64; l++) if (lds[(tid & ~63u) + l]) m |= 1ull << l;
+    __syncthreads();
+    return m;
+#else
+    (void)lds;
+    return __ballot(p);
+#endif
+}
+
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_count_kernel(const uint8_t* flags, uint64_t count, uint32_t* tile_counts) {
+    __shared__ uint32_t bl[MP_T];
+    __shared__ uint32_t wc[MP_WAVES];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint64_t base = (uint64_t)blockIdx.x * MP_TILE;
+    uint32_t mine = 0;
+    for (uint32_t e = 0; e < MP_E; e++) {
+        const uint64_t i = base + (uint64_t)e * MP_T + tid;
+        mine += (uint32_t)__builtin_popcountll(mp_ballot(i < count && flags[i], bl));
+    }
+    if (lane == 0) wc[wave] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t s = 0;
+        for (uint32_t w = 0; w < MP_WAVES; w++) s += wc[w];
+        tile_counts[blockIdx.x] = s;
+    }
+}
+// exclusive scan of the n_tiles counts in place (one workgroup), the total at counts[n_tiles]
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_scan_kernel(uint32_t* counts, uint32_t n_tiles) {
+    __shared__ uint32_t s[MP_T];
+    const uint32_t tid = threadIdx.x, per = (n_tiles + MP_T - 1) / MP_T;
+    const uint32_t lo = tid * per < n_tiles ? tid * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += counts[i];
+    s[tid] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < MP_T; d <<= 1) {
+        const uint32_t v = tid >= d ? s[tid - d] : 0u;
+        __syncthreads();
+        s[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = s[tid] - sum;
+    for (uint32_t i = lo; i < hi; i++) { const uint32_t c = counts[i]; counts[i] = run; run += c; }
+    if (tid == MP_T - 1) counts[n_tiles] = s[MP_T - 1];
+}
+// flagged index i -> out[its rank among the flagged]: tile offset + earlier rounds of the tile + earlier waves of the round + earlier lanes of the wave
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_scatter_kernel(const uint8_t* flags, uint64_t count, const uint32_t* tile_offsets, uint32_t* out) {
+    __shared__ uint32_t bl[MP_T];
+    __shared__ uint32_t wc[MP_E][MP_WAVES];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint64_t base = (uint64_t)blockIdx.x * MP_TILE;
+    uint64_t masks[MP_E];
+    for (uint32_t e = 0; e < MP_E; e++) {
+        const uint64_t i = base + (uint64_t)e * MP_T + tid;
+        masks[e] = mp_ballot(i < count && flags[i], bl);
+        if (lane == 0) wc[e][wave] = (uint32_t)__builtin_popcountll(masks[e]);
+    }
+    __syncthreads();
+    uint32_t pos = tile_offsets[blockIdx.x];
+    for (uint32_t e = 0; e < MP_E; e++) {
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; w++) before += wc[e][w];
+        if ((masks[e] >> lane) & 1ull)
+            out[pos + before + (uint32_t)__builtin_popcountll(masks[e] & ((1ull << lane) - 1ull))] = (uint32_t)(base + (uint64_t)e * MP_T + tid);
+        for (uint32_t w = 0; w < MP_WAVES; w++) pos += wc[e][w];
+    }
+}
+
+// gate values of the rows < u -> flags (the interpreter's output is fully reduced)
+ZK_KERNEL void mp_nonzero_kernel(const void* vals, uint32_t u, uint8_t* flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < u) flags[i] = Fr::is_zero(load_u256(vals, i)) ? 0 : 1;
+}
+
+ZK_HD bool mp_less(const u256& a, const u256& b) {
+    for (int w = 7; w >= 0; w--)
+        if (a.v[w] != b.v[w]) return a.v[w] < b.v[w];
+    return false;
+}
+// the rows < u of a compressed table column, padded to n = 2^k with all-ones (above every reduced value: the network sorts powers of two)
+ZK_KERNEL void mp_table_init_kernel(const void* src, uint32_t u, uint32_t n, void* dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u256 v;
+    if (i < u) v = load_u256(src, i);
+    else for (int w = 0; w < 8; w++) v.v[w] = 0xffffffffu;
+    store_u256(dst, i, v);
+}
+// one compare-exchange step of the bitonic network over n values: stage `size` (ascending where index & size == 0), partner distance `dist` >= MP_LOCAL
+ZK_KERNEL void mp_bitonic_step_kernel(void* v, uint32_t n, uint32_t size, uint32_t dist) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n / 2) return;
+    const uint32_t lo = ((t & ~(dist - 1u)) << 1) | (t & (dist - 1u)), hi = lo | dist;
+    const u256 a = load_u256(v, lo), b = load_u256(v, hi);
+    if (mp_less(b, a) == ((lo & size) == 0)) { store_u256(v, lo, b); store_u256(v, hi, a); }
+}
+// the steps of stages size_lo .. size_hi whose partner distance is below 2 * blockDim.x, on tiles of 2 * blockDim.x values in LDS
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_bitonic_local_kernel(void* v, uint32_t size_lo, uint32_t size_hi) {
+    __shared__ uint4 s[2 * MP_LOCAL];
+    const uint32_t tid = threadIdx.x, T = blockDim.x, base = blockIdx.x * 2 * T;
+    const uint4* g = reinterpret_cast<const uint4*>(v) + 2 * (size_t)base;
+    for (uint32_t j = tid; j < 4 * T; j += T) s[j] = g[j];
+    __syncthreads();
+    for (uint32_t size = size_lo; size <= size_hi; size <<= 1) {
+        for (uint32_t dist = size / 2 < T ? size / 2 : T; dist > 0; dist >>= 1) {
+            const uint32_t lo = ((tid & ~(dist - 1u)) << 1) | (tid & (dist - 1u)), hi = lo | dist;
+            u256 a, b;
+            const uint4 a0 = s[2 * lo], a1 = s[2 * lo + 1], b0 = s[2 * hi], b1 = s[2 * hi + 1];
+            a.v[0] = a0.x; a.v[1] = a0.y; a.v[2] = a0.z; a.v[3] = a0.w; a.v[4] = a1.x; a.v[5] = a1.y; a.v[6] = a1.z; a.v[7] = a1.w;
+            b.v[0] = b0.x; b.v[1] = b0.y; b.v[2] = b0.z; b.v[3] = b0.w; b.v[4] = b1.x; b.v[5] = b1.y; b.v[6] = b1.z; b.v[7] = b1.w;
+            if (mp_less(b, a) == (((base + lo) & size) == 0)) { s[2 * lo] = b0; s[2 * lo + 1] = b1; s[2 * hi] = a0; s[2 * hi + 1] = a1; }
+            __syncthreads();
+        }
+    }
+    uint4* o = reinterpret_cast<uint4*>(v) + 2 * (size_t)base;
+    for (uint32_t j = tid; j < 4 * T; j += T) o[j] = s[j];
+}
+// flags[r] = input row r < u has no equal among the n = 2^k sorted table values (lower bound by halving)
+ZK_KERNEL void mp_search_kernel(const void* in, const void* sorted, uint32_t k, uint32_t u, uint8_t* flags) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= u) return;
+    const u256 x = load_u256(in, r);
+    uint32_t pos = 0;
+    for (uint32_t b = (1u << k) >> 1; b; b >>= 1)
+        if (mp_less(load_u256(sorted, pos + b - 1), x)) pos += b;
+    flags[r] = Fr::eq(load_u256(sorted, pos), x) ? 0 : 1;
+}
+// flags[j * n + row] = cell (j, row) differs from the cell the copy mapping sends it to; an entry outside the mapping's range sets *bad and is not read
+ZK_KERNEL void mp_copy_kernel(const void* const* cols, const uint32_t* map_c, const uint32_t* map_r, uint32_t n_cols, uint32_t k, uint8_t* flags, uint32_t* bad) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ((uint64_t)n_cols << k)) return;
+    const uint32_t j = (uint32_t)(e >> k), row = (uint32_t)e & ((1u << k) - 1u), cj = map_c[e], rj = map_r[e];
+    uint8_t f = 0;
+    if (cj >= n_cols || rj >= (1u << k)) atomicOr(bad, 1u);
+    else if (cj != j || rj != row) f = Fr::eq(Fr::normalize(load_u256(cols[j], row)), Fr::normalize(load_u256(cols[cj], rj))) ? 0 : 1;
+    flags[e] = f;
+}
+
+struct MpMem {                                   // every temporary of one call, returned to the device when the call ends (error returns included)
+    std::list<DevTmp> held;
+    void* get(size_t bytes) {
+        held.emplace_back();
+        if (hipMalloc(&held.back().p, bytes ? bytes : 32) != hipSuccess) { held.back().p = nullptr; return nullptr; }
+        return held.back().p;
+    }
+};
+struct MpPrograms {                              // program handles of one call, released when it ends
+    zk_ctx* ctx; std::vector<uint64_t> h;
+    ~MpPrograms() { for (uint64_t p : h) if (p) (void)quotient_program_release(ctx, p); }
+};
+
+// flags[0 .. count) -> the ascending list of the flagged indices (device memory from `mem`) and its length
+int mp_compact(zk_ctx* ctx, MpMem& mem, const uint8_t* d_flags, uint64_t count, uint32_t** list, uint32_t* total) {
+    const uint32_t tiles = (uint32_t)((count + MP_TILE - 1) / MP_TILE);
+    *total = 0;
+    *list = nullptr;
+    if (!tiles) return ZK_OK;
+    uint32_t* cnt = (uint32_t*)mem.get(((size_t)tiles + 1) * 4);
+    if (!cnt) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+    ZK_LAUNCH(mp_count_kernel, tiles, MP_T, 0, ctx->stream, d_flags, count, cnt);
+    ZK_CHECK_LAUNCH();
+    ZK_LAUNCH(mp_scan_kernel, 1, MP_T, 0, ctx->stream, cnt, tiles);
+    ZK_CHECK_LAUNCH();
+    ZK_HIP(hipMemcpyAsync(total, cnt + tiles, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!*total) return ZK_OK;
+    *list = (uint32_t*)mem.get((size_t)*total * 4);
+    if (!*list) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+    ZK_LAUNCH(mp_scatter_kernel, tiles, MP_T, 0, ctx->stream, d_flags, count, (const uint32_t*)cnt, *list);
+    ZK_CHECK_LAUNCH();
+    return ZK_OK;
+}
+
+// bitonic sort of n = 2^k values in place (ascending, full 256-bit order)
+int mp_sort(zk_ctx* ctx, void* d_v, uint32_t k) {
+    const uint32_t n = 1u << k, T = std::min<uint32_t>(MP_T, n / 2), L = 2 * T;
+    ZK_LAUNCH(mp_bitonic_local_kernel, n / L, T, 0, ctx->stream, d_v, 2u, L);
+    ZK_CHECK_LAUNCH();
+    for (uint32_t size = 2 * L; size <= n; size <<= 1) {
+        for (uint32_t dist = size / 2; dist >= L; dist >>= 1) {
+            ZK_LAUNCH(mp_bitonic_step_kernel, (n / 2 + 255) / 256, 256, 0, ctx->stream, d_v, n, size, dist);
+            ZK_CHECK_LAUNCH();
+        }
+        ZK_LAUNCH(mp_bitonic_local_kernel, n / L, T, 0, ctx->stream, d_v, size, size);
+        ZK_CHECK_LAUNCH();
+    }
+    return ZK_OK;
+}
+
+u256 mp_random_nonzero(std::mt19937_64& g) {     // a uniform non-zero field element (Montgomery form or not: the same distribution)
+    for (;;) {
+        u256 x;
+        for (int i = 0; i < 8; i += 2) { const uint64_t w = g(); x.v[i] = (uint32_t)w; x.v[i + 1] = (uint32_t)(w >> 32); }
+        x.v[7] &= 0x3fffffffu;                                        // < 2^254 < 2p
+        x = Fr::reduce_once(x);
+        if (!Fr::is_zero(x)) return x;
+    }
+}
+
+struct MpTimer {                                 // one pass under HIP events (zk_timing_enable): "mock_copies", "mock_gates", "mock_gate_rows", "mock_lookups"
+    EvTimer t;
+    MpTimer(zk_ctx* ctx, const char* label) : t(ctx, label) {}
+    void done() { t.stop(); t.resolve(); }
+};
+}  // namespace
+
+int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written) {
+    if (!d) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: null descriptor");
+    if (d->struct_size != sizeof(zk_mock_desc))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: zk_mock_desc.struct_size %u, expected %zu (ABI version %u)", d->struct_size, sizeof(zk_mock_desc), ZK_ABI_VERSION);
+    if (!counts || (cap && !out)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: null counts / output");
+    const uint32_t k = d->k, F = d->n_fixed, A = d->n_advice, I = d->n_instance, L = d->n_lookups, M = d->n_perm_columns;
+    if (k < 2 || k > 26 || (uint64_t)d->blinding_factors + 1 >= (1ull << k))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: k = %u with %u blinding factors", k, d->blinding_factors);
+    const uint32_t n = 1u << k, u = n - d->blinding_factors - 1;
+    const size_t col_bytes = (size_t)32 << k;
+    if ((F && !d->fixed_values) || (A && !d->advice_values) || (L && (!d->lookup_input_zkq1 || !d->lookup_input_zkq1_len || !d->lookup_table_zkq1 || !d->lookup_table_zkq1_len)) ||
+        (M && (!d->perm_columns || !d->perm_map_column || !d->perm_map_row)) || !d->evaluator_zkq1)
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: missing column / program / mapping array");
+    for (uint32_t i = 0; i < F; i++) if (!d->fixed_values[i]) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: fixed column %u is NULL", i);
+    for (uint32_t i = 0; i < A; i++) if (!d->advice_values[i]) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: advice column %u is NULL", i);
+    for (uint32_t j = 0; j < M; j++) {
+        const uint32_t ty = d->perm_columns[2 * j], ix = d->perm_columns[2 * j + 1];
+        if (ty > 2 || ix >= (ty == 0 ? A : ty == 1 ? F : I)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: permutation column %u = (%u, %u) out of range", j, ty, ix);
+    }
+    if (((uint64_t)M << k) >= (1ull << 32) || (uint64_t)L * u >= (1ull << 32)) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_verify: more than 2^32 cells to check in one pass");
+    // every program's header before any work: the column counts are what the column tables are built from
+    auto header = [&](const void* blob, size_t len, bool evaluator, const char* what, uint32_t i) -> int {
+        if (!blob || len < 48 || (len & 3)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: bad %s blob %u", what, i);
+        uint32_t w[7];
+        memcpy(w, blob, sizeof w);
+        if (w[0] != 0x31514B5Au) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_verify: %s blob %u: bad magic", what, i);
+        if (w[6]) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_verify: %s blob %u declares %u challenges (multi-phase circuits are not modelled)", what, i, w[6]);
+        if (w[1] != k || (!evaluator && w[2] != k)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: %s blob %u is for k = %u / extended_k = %u, not k = %u", what, i, w[1], w[2], k);
+        if (w[3] != F || w[4] != A || w[5] != I) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: %s blob %u has %u / %u / %u fixed / advice / instance columns, the descriptor %u / %u / %u",
+                                                                   what, i, w[3], w[4], w[5], F, A, I);
+        return ZK_OK;
+    };
+    int rc = header(d->evaluator_zkq1, d->evaluator_zkq1_len, true, "evaluator", 0);
+    for (uint32_t l = 0; l < L && !rc; l++) {
+        rc = header(d->lookup_input_zkq1[l], d->lookup_input_zkq1_len[l], false, "lookup input", l);
+        if (!rc) rc = header(d->lookup_table_zkq1[l], d->lookup_table_zkq1_len[l], false, "lookup table", l);
+    }
+    if (rc) return rc;
+    for (uint32_t c = 0; c < I; c++) {
+        const uint32_t len = d->instance_lens ? d->instance_lens[c] : 0;
+        if (len > n || (len && (!d->instances || !d->instances[c]))) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: instance column %u: %u values", c, len);
+    }
+
+    MpMem mem;
+    MpPrograms progs{ctx, {}};
+    hipStream_t st = ctx->stream;
+    // ---- columns on the device: fixed / advice as given or uploaded, instances to Montgomery form, one zero column for the l_* slots the programs never read ----
+    std::vector<const void*> fx(F), ad(A), in(I);
+    for (uint32_t i = 0; i < F + A; i++) {
+        const void* src = i < F ? d->fixed_values[i] : d->advice_values[i - F];
+        const void*& dst = i < F ? fx[i] : ad[i - F];
+        if (d->values_on_device) { dst = src; continue; }
+        void* p = mem.get(col_bytes);
+        if (!p) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+        ZK_HIP(hipMemcpyAsync(p, src, col_bytes, hipMemcpyHostToDevice, st));
+        dst = p;
+    }
+    std::vector<u256> host_col;
+    for (uint32_t c = 0; c < I; c++) {
+        const uint32_t len = d->instance_lens ? d->instance_lens[c] : 0;
+        host_col.assign(n, Fr::zero());
+        for (uint32_t i = 0; i < len; i++) {
+            u256 v;
+            memcpy(&v, (const char*)d->instances[c] + 32 * (size_t)i, 32);
+            if (!Fr::eq(Fr::reduce_once(v), v)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: instance %u of column %u is not canonical", i, c);
+            host_col[i] = Fr::to_mont(v);
+        }
+        void* p = mem.get(col_bytes);
+        if (!p) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+        ZK_HIP(hipMemcpyAsync(p, host_col.data(), col_bytes, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipStreamSynchronize(st));                             // (host_col is refilled for the next column)
+        in[c] = p;
+    }
+    void* zero_col = mem.get(col_bytes);
+    void* work = mem.get(col_bytes);
+    if (!zero_col || !work) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+    ZK_HIP(hipMemsetAsync(zero_col, 0, col_bytes, st));
+
+    std::random_device rd;
+    std::mt19937_64 rng(((uint64_t)rd() << 32) ^ rd());
+    const u256 one = Fr::one(), r = mp_random_nonzero(rng), theta = mp_random_nonzero(rng);
+    zk_quotient_args qa;
+    ZK_STRUCT_INIT(qa);
+    qa.fixed = fx.data(); qa.advice = ad.data(); qa.instance = in.data();
+    qa.l0 = qa.l_last = qa.l_active_row = zero_col;
+    qa.challenges = &one; qa.beta = &one; qa.gamma = &one; qa.theta = &theta; qa.y = &r;
+    const uint32_t blk = 256;
+
+    // ---- 4. copies (first: a mapping out of range is an argument error, found before the other passes run) ----------------------------------------------------
+    uint32_t n_copy = 0, *copy_list = nullptr;
+    if (M) {
+        MpTimer t(ctx, "mock_copies");
+        const size_t cells = (size_t)M << k;
+        std::vector<const void*> cp(M);
+        for (uint32_t j = 0; j < M; j++) {
+            const uint32_t ty = d->perm_columns[2 * j], ix = d->perm_columns[2 * j + 1];
+            cp[j] = ty == 0 ? ad[ix] : ty == 1 ? fx[ix] : in[ix];
+        }
+        void* d_cp = mem.get((size_t)M * sizeof(void*));
+        uint32_t* d_mc = (uint32_t*)mem.get(cells * 4);
+        uint32_t* d_mr = (uint32_t*)mem.get(cells * 4);
+        uint8_t* flags = (uint8_t*)mem.get(cells);
+        uint32_t* d_bad = (uint32_t*)mem.get(4);
+        if (!d_cp || !d_mc || !d_mr || !flags || !d_bad) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+        ZK_HIP(hipMemcpyAsync(d_cp, cp.data(), (size_t)M * sizeof(void*), hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_mc, d->perm_map_column, cells * 4, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_mr, d->perm_map_row, cells * 4, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemsetAsync(d_bad, 0, 4, st));
+        ZK_LAUNCH(mp_copy_kernel, (uint32_t)((cells + blk - 1) / blk), blk, 0, st, (const void* const*)d_cp, d_mc, d_mr, M, k, flags, d_bad);
+        ZK_CHECK_LAUNCH();
+        uint32_t bad = 0;
+        ZK_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        if (bad) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: a copy-mapping entry is out of range (column >= %u or row >= 2^%u)", M, k);
+        rc = mp_compact(ctx, mem, flags, cells, &copy_list, &n_copy);
+        if (rc) return rc;
+        t.done();
+    }
+
+    // ---- 1 + 2. gates: detection over every row, attribution on the failing rows ---------------------------------------------------------------------------
+    uint32_t n_polys = 0, n_rows = 0, words = 0;
+    std::vector<uint32_t> rows, bits;
+    {
+        uint64_t gp = 0;
+        rc = quotient_program_load_gates(ctx, d->evaluator_zkq1, d->evaluator_zkq1_len, &gp, &n_polys);
+        if (rc) return rc;
+        progs.h.push_back(gp);
+        words = (n_polys + 31) / 32;
+    }
+    if (n_polys) {
+        uint32_t* list = nullptr;
+        {
+            MpTimer t(ctx, "mock_gates");
+            qa.out = work;
+            rc = quotient_run(ctx, progs.h.back(), &qa, -1, 0, 0, 0, 0, 0);
+            if (rc) return rc;
+            uint8_t* flags = (uint8_t*)mem.get(u);
+            if (!flags) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+            ZK_LAUNCH(mp_nonzero_kernel, (u + blk - 1) / blk, blk, 0, st, (const void*)work, u, flags);
+            ZK_CHECK_LAUNCH();
+            rc = mp_compact(ctx, mem, flags, u, &list, &n_rows);
+            if (rc) return rc;
+            t.done();
+        }
+        if (n_rows) {
+            MpTimer t(ctx, "mock_gate_rows");
+            uint32_t* d_bits = (uint32_t*)mem.get((size_t)n_rows * words * 4);
+            if (!d_bits) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+            const QuotRowList rl{list, n_rows, d_bits, words};
+            rc = quotient_run(ctx, progs.h.back(), &qa, -1, 0, 0, 0, 0, 0, &rl);
+            if (rc) return rc;
+            rows.resize(n_rows);
+            bits.resize((size_t)n_rows * words);
+            ZK_HIP(hipMemcpyAsync(rows.data(), list, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+            ZK_HIP(hipMemcpyAsync(bits.data(), d_bits, bits.size() * 4, hipMemcpyDeviceToHost, st));
+            ZK_HIP(hipStreamSynchronize(st));
+            t.done();
+        }
+    }
+
+    // ---- 3. lookups: compress, sort each distinct table once, search every input --------------------------------------------------------------------------
+    uint32_t n_lookup = 0, *lookup_list = nullptr;
+    if (L) {
+        MpTimer t(ctx, "mock_lookups");
+        uint8_t* flags = (uint8_t*)mem.get((size_t)L * u);
+        if (!flags) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+        std::map<std::string, void*> sorted;                          // table blob -> its sorted compressed column (byte-equal blobs share one)
+        auto compress = [&](const void* blob, size_t len, void* dst) -> int {
+            uint64_t p = 0;
+            int rc_ = quotient_program_load(ctx, blob, len, &p);
+            if (rc_) return rc_;
+            progs.h.push_back(p);
+            qa.out = dst;
+            rc_ = quotient_run(ctx, p, &qa, -1, 0, 0, 0, 0, 0);
+            progs.h.back() = 0;
+            (void)quotient_program_release(ctx, p);
+            return rc_;
+        };
+        for (uint32_t l = 0; l < L; l++) {
+            const std::string key((const char*)d->lookup_table_zkq1[l], d->lookup_table_zkq1_len[l]);
+            auto it = sorted.find(key);
+            if (it == sorted.end()) {
+                void* s = mem.get(col_bytes);
+                if (!s) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
+                rc = compress(d->lookup_table_zkq1[l], d->lookup_table_zkq1_len[l], work);
+                if (rc) return rc;
+                ZK_LAUNCH(mp_table_init_kernel, (n + blk - 1) / blk, blk, 0, st, (const void*)work, u, n, s);
+                ZK_CHECK_LAUNCH();
+                rc = mp_sort(ctx, s, k);
+                if (rc) return rc;
+                it = sorted.emplace(key, s).first;
+            }
+            rc = compress(d->lookup_input_zkq1[l], d->lookup_input_zkq1_len[l], work);
+            if (rc) return rc;
+            ZK_LAUNCH(mp_search_kernel, (u + blk - 1) / blk, blk, 0, st, (const void*)work, (const void*)it->second, k, u, flags + (size_t)l * u);
+            ZK_CHECK_LAUNCH();
+        }
+        rc = mp_compact(ctx, mem, flags, (uint64_t)L * u, &lookup_list, &n_lookup);
+        if (rc) return rc;
+        t.done();
+    }
+
+    // ---- records: gates by (row, polynomial), lookups by (lookup, row), copies by (column, row); the first `cap` of them -------------------------------------
+    uint64_t n_gate = 0;
+    for (uint32_t w : bits) n_gate += (uint64_t)__builtin_popcount(w);
+    counts[0] = n_gate; counts[1] = n_lookup; counts[2] = n_copy;
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_rows && at < cap; i++)
+        for (uint32_t p = 0; p < n_polys && at < cap; p++)
+            if ((bits[(size_t)i * words + p / 32] >> (p & 31)) & 1u) out[at++] = zk_mock_failure{0, p, rows[i], 0, 0};
+    std::vector<uint32_t> idx;
+    const size_t take_l = std::min<size_t>(cap - at, n_lookup);
+    if (take_l) {
+        idx.resize(take_l);
+        ZK_HIP(hipMemcpyAsync(idx.data(), lookup_list, take_l * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        for (uint32_t e : idx) out[at++] = zk_mock_failure{1, e / u, e % u, 0, 0};
+    }
+    const size_t take_c = std::min<size_t>(cap - at, n_copy);
+    if (take_c) {
+        idx.resize(take_c);
+        ZK_HIP(hipMemcpyAsync(idx.data(), copy_list, take_c * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        for (uint32_t e : idx) out[at++] = zk_mock_failure{2, e >> k, e & (n - 1), d->perm_map_column[e], d->perm_map_row[e]};
+    }
+    if (n_written) *n_written = at;
+    return ZK_OK;
+}
+
+}  // namespace zk

@@ -50,4 +50,14 @@ int quot_jit_build(zk_ctx* ctx, QuotProgram& P);                                
 bool quot_jit_ready(const QuotProgram& P);
 uint32_t quot_jit_kernel_count(const QuotProgram& P);
 int quot_jit_launch(zk_ctx* ctx, const QuotProgram& P, const QuotArgs& q, uint64_t rows, uint32_t threads);
+
+// Row-list mode of quotient_run (mockprover.hip, gate attribution): the program runs on rows[0 .. n) of its domain only, and instead of the value every thread
+// writes one bit per fold of the accumulator: bit f of bits[i * words + f / 32] = the f-th folded term of row rows[i] is non-zero after full reduction.  For the
+// program of quotient_program_load_gates the folds are exactly the gate polynomials, in cs.gates order.
+struct QuotRowList { const uint32_t* rows; uint32_t n; uint32_t* bits; uint32_t words; };
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
+                 const QuotRowList* rl = nullptr);
+// The custom gates of an Evaluator blob (ZKQ1) alone, compiled at extended_k = k: value(row) = sum_i y^(E-1-i) gate_i(row), rotations mod 2^k (the permutation and
+// the lookups of the blob are dropped).  *n_polys = E, the parts of the blob's final Horner(previous, gates, y); E = 0 loads nothing (*prog = 0).
+int quotient_program_load_gates(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog, uint32_t* n_polys);
 }  // namespace zk

@@ -132,6 +132,78 @@ ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) ZK_WAVES_PER_EU(4) quotient_kernel(QuotArgs
     store_u256(q.out, oidx, Fr::normalize(acc));
 }
 
+// A micro-op that folds one identity into the accumulator: acc = acc * y^e + term (M_MULADD with the accumulator as first operand and destination), or
+// acc = acc * y^e + a * b as fuse_folds_pass leaves the fold of a product (M_FOLD2)
+ZK_HD bool quot_is_fold(uint32_t w0, uint32_t sa) {
+    const uint32_t op = w0 & 0xffu;
+    return op == M_FOLD2 || (op == M_MULADD && ((w0 >> 8) & 0xffu) && (sa >> 28) == K_ACC);
+}
+
+// Row-list mode (QuotRowList, mockprover.hip): thread i runs the program on row rows[i] and records, fold by fold, whether the folded term is non-zero after full
+// reduction (bit f of bits[i * words + f / 32]).  The micro-ops of quotient_kernel without its software pipelining: it runs on a list of failing rows, not on a
+// domain.  Programs that read X (the permutation argument) are refused by quotient_run.
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) quotient_rows_kernel(QuotArgs q, const uint32_t* rows, uint32_t n_rows, uint32_t* bits, uint32_t words) {
+    ZK_DYN_SHARED(uint4, smem);
+    const uint32_t T = blockDim.x, tid = threadIdx.x, i = blockIdx.x * T + tid;
+    if (i >= n_rows) return;
+    const uint32_t idx0 = rows[i], mask = (1u << q.size_log) - 1u;
+    u256 acc = Fr::zero(), rg0 = Fr::zero();
+    auto rd = [&](uint32_t src) -> u256 {
+        const uint32_t kind = src >> 28, pay = src & 0x0fffffffu;
+        switch (kind) {
+            case K_COL: return load_u256(q.cols[pay >> 8], (idx0 + q.rot_off[pay & 0xffu]) & mask);
+            case K_CONST: return load_u256(q.consts, pay);
+            case K_ACC: return acc;
+            case K_SLOT: {
+                if (pay < QUOT_NREG) return rg0;
+                const uint32_t ls = pay - QUOT_NREG;
+                const uint4 l = smem[(2 * ls) * T + tid], h = smem[(2 * ls + 1) * T + tid];
+                u256 o;
+                o.v[0] = l.x; o.v[1] = l.y; o.v[2] = l.z; o.v[3] = l.w; o.v[4] = h.x; o.v[5] = h.y; o.v[6] = h.z; o.v[7] = h.w;
+                return o;
+            }
+            default: return Fr::zero();
+        }
+    };
+    uint32_t fold = 0, word = 0;
+    for (uint32_t pc = 0; pc < q.n_instr; pc++) {
+        const uint4 ins = q.code[pc];
+        const uint32_t w0 = ZK_UNIFORM(ins.x), sa = ZK_UNIFORM(ins.y), sb = ZK_UNIFORM(ins.z), sc = ZK_UNIFORM(ins.w), op = w0 & 0xffu;
+        const u256 a = rd(sa);
+        u256 res;
+        switch (op) {
+            case M_ADD: res = Fr::red2p(Fr::add_lazy(a, rd(sb))); break;
+            case M_SUB: res = Fr::sub2(a, rd(sb)); break;
+            case M_MUL: res = Fr::mul_lazy(a, rd(sb)); break;
+            case M_SQR: res = Fr::sqr_lazy(a); break;
+            case M_DBL: res = Fr::dbl2(a); break;
+            case M_NEG: res = Fr::neg2(a); break;
+            case M_MULADD: res = Fr::red2p(Fr::add_lazy(Fr::mul_lazy(a, rd(sb)), rd(sc))); break;
+            case M_FOLD2: res = Fr::mul2_add_2p(acc, rd(sc), a, rd(sb)); break;
+            default: res = a; break;
+        }
+        if (quot_is_fold(w0, sa)) {
+            const u256 term = op == M_FOLD2 ? Fr::mul_lazy(a, rd(sb)) : rd(sc);
+            if (!Fr::is_zero(Fr::normalize(term))) word |= 1u << (fold & 31u);
+            if ((fold & 31u) == 31u && fold / 32 < words) { bits[(size_t)i * words + fold / 32] = word; word = 0; }
+            fold++;
+        }
+        if ((w0 >> 8) & 0xffu) {
+            acc = res;
+        } else {
+            const uint32_t slot = w0 >> 16;
+            if (slot < QUOT_NREG) {
+                rg0 = res;
+            } else {
+                const uint32_t ls = slot - QUOT_NREG;
+                smem[(2 * ls) * T + tid] = make_uint4(res.v[0], res.v[1], res.v[2], res.v[3]);
+                smem[(2 * ls + 1) * T + tid] = make_uint4(res.v[4], res.v[5], res.v[6], res.v[7]);
+            }
+        }
+    }
+    if ((fold & 31u) && fold / 32 < words) bits[(size_t)i * words + fold / 32] = word;
+}
+
 // ------------------------------------------------------------------------------------------------
 // compiler: ZKQ1 blob -> micro-program
 // ------------------------------------------------------------------------------------------------
@@ -824,6 +896,50 @@ int quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* p
     ctx->programs[*prog] = P;
     return ZK_OK;
 }
+// The custom gates of an Evaluator blob alone at extended_k = k (mockprover.hip): the header is rewritten (extended_k = k, no permutation columns, no lookups) and
+// the custom-gate graph compiled as it is.  Its final Horner(previous, gates, y) folds the E gate polynomials into the accumulator one by one — the folds the
+// row-list mode reads back, so the compiled program must hold exactly E of them.  No degree split and no generated kernels: the program runs on 2^k rows.
+int quotient_program_load_gates(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog, uint32_t* n_polys) {
+    *prog = 0;
+    *n_polys = 0;
+    if (!blob || len < 48 || (len & 3)) return ctx->fail(ZK_ERR_ARG, "gates program: bad blob pointer/length");
+    std::vector<uint32_t> w(len / 4);
+    memcpy(w.data(), blob, len);
+    if (w[0] != 0x31514B5Au) return ctx->fail(ZK_ERR_PROGRAM, "quotient program: bad magic");
+    const uint32_t npc = w[9];
+    if (npc > 4096 || 11 + 2 * (size_t)npc > w.size()) return ctx->fail(ZK_ERR_PROGRAM, "quotient program: truncated header");
+    std::vector<uint32_t> g(w.begin(), w.begin() + 10);             // magic .. n_perm_columns
+    g[2] = g[1];
+    g[9] = 0;
+    g.push_back(0);                                                  // n_lookups
+    g.insert(g.end(), w.begin() + 11 + 2 * (size_t)npc, w.end());    // the custom-gate graph (the lookup graphs behind it are not read)
+    {
+        Reader r{g.data() + 11, g.size() - 11};
+        Graph custom;
+        if (!read_graph(r, custom)) return ctx->fail(ZK_ERR_PROGRAM, "quotient program: malformed custom-gate graph");
+        if (custom.calcs.empty()) return ZK_OK;
+        const Calc& last = custom.calcs.back();
+        if (last.op != OP_HORNER || last.s0.kind != VS_PREV || last.s1.kind != VS_Y)
+            return ctx->fail(ZK_ERR_PROGRAM, "gates program: the custom-gate graph does not end in Horner(previous, gates, y)");
+        *n_polys = (uint32_t)last.parts.size();
+    }
+    if (!*n_polys) return ZK_OK;
+    std::shared_ptr<QuotProgram> P(new QuotProgram());
+    P->device = ctx->device;
+    int rc = compile_program(ctx, g.data(), g.size(), *P);
+    uint32_t folds = 0;
+    if (!rc) for (const uint4& ins : P->code) if (quot_is_fold(ins.x, ins.y)) folds++;
+    if (!rc && (folds != *n_polys || P->uses_xpow)) rc = ctx->fail(ZK_ERR_PROGRAM, "gates program: %u folds for %u gate polynomials", folds, *n_polys);
+    if (!rc && (size_t)(P->n_slots > QUOT_NREG ? P->n_slots - QUOT_NREG : 0) * 64 * 32 > 160 * 1024)
+        rc = ctx->fail(ZK_ERR_LIMIT, "gates program needs %u live intermediates; this build keeps at most 80 in LDS", P->n_slots);
+    if (rc) { *n_polys = 0; return rc; }
+    hipError_t e = hipMalloc(&P->d_code, P->code.size() * 16 + 16);
+    if (e == hipSuccess) e = hipMemcpy(P->d_code, P->code.data(), P->code.size() * 16, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { *n_polys = 0; return ctx->fail(ZK_ERR_HIP, "gates program: device allocation failed"); }
+    *prog = ctx->next_handle++;
+    ctx->programs[*prog] = P;
+    return ZK_OK;
+}
 // a handle of `ctx` onto a program another context of the same device loaded: one compiled program (and one proving key) per process, however many
 // contexts prove concurrently.  Called WITHOUT either context's lock held (capi.hip): takes the owner's, then ctx's.
 int quotient_program_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_prog, uint64_t* prog) {
@@ -895,6 +1011,7 @@ void release_programs(zk_ctx* ctx) {
 int quotient_set_lds_attr() {
 #ifndef ZK_EMU
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #endif
     return 0;
 }
@@ -907,13 +1024,18 @@ int quotient_set_lds_attr() {
 // part: 0 = every identity; 1 / 2 = the high / low part of a program that has a degree split (QuotProgram::part_hi / part_lo).  low_cosets > 0 (part 2, coset < 0): the
 // columns are the whole extended domain but only the rows of its cosets 0 .. low_cosets-1 are evaluated — thread i of coset j reads row i * 2^(ek-k) + j — and
 // out receives low_cosets x n values, coset-major (what zk_cosets_to_pieces_dev takes).
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate) {
+// rl: row-list mode (quotient.h, QuotRowList) — a program of extended_k = k that does not read X, on the whole domain.
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
+                 const QuotRowList* rl) {
     auto it = ctx->programs.find(prog);
     if (it == ctx->programs.end()) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: unknown program %llu", (unsigned long long)prog);
     if (part && (!it->second->part_hi || !it->second->part_lo)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_part_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
     QuotProgram& P = part == 1 ? *it->second->part_hi : part == 2 ? *it->second->part_lo : *it->second;
     if (low_cosets && (part != 2 || coset >= 0 || row_count || (low_cosets & (low_cosets - 1)) || low_cosets > (1u << (P.ek - P.k))))
         return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_low_dev: %u cosets of the extended domain: a power of two, at most 2^(extended_k - k), low part only", low_cosets);
+    if (rl && (coset >= 0 || row_count || part || low_cosets || accumulate || P.ek != P.k || P.uses_xpow || !rl->rows || !rl->bits || (uint64_t)rl->words * 32 < P.folds_taken))
+        return ctx->fail(ZK_ERR_ARG, "quotient_run: a row list takes a program of extended_k = k that does not read X, on the whole domain");
+    if (rl && !rl->n) return ZK_OK;
     if (!a || !a->out || !a->l0 || !a->l_last || !a->l_active_row || !a->beta || !a->gamma || !a->theta || !a->y)
         return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: null argument");
     if (a->n_sets != P.n_sets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: n_sets = %u but the program has %u permutation sets", a->n_sets, P.n_sets);
@@ -1013,7 +1135,10 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
     const size_t lds = (size_t)lds_slots * T * 32;
     if (lds > 160 * 1024) return ctx->fail(ZK_ERR_LIMIT, "quotient program needs %zu bytes of LDS", lds);
     EvTimer tq(ctx, "quotient");
-    if (quot_jit_ready(P)) {                                          // (the PROGRAM records whether it was generated: contexts that borrow it need no tunable of their own)
+    if (rl) {
+        ZK_LAUNCH(quotient_rows_kernel, (rl->n + T - 1) / T, T, lds, st, q, rl->rows, rl->n, rl->bits, rl->words);
+        ZK_CHECK_LAUNCH();
+    } else if (quot_jit_ready(P)) {                                          // (the PROGRAM records whether it was generated: contexts that borrow it need no tunable of their own)
         uint32_t Tj = (uint32_t)std::min(ctx->tune.quot_threads, 256);
         if (Tj > rows) Tj = (uint32_t)rows;
         int rcj = quot_jit_launch(ctx, P, q, rows, Tj);

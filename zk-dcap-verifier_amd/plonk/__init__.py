@@ -6,12 +6,13 @@ circuits/src/sgx_dcap_verifier.rs:803,807,814-822), as a host-side mirror over t
     create_proof(params, pk, advice_columns, instances, rng, transcript)                 plonk::create_proof + ProverSHPLONK (Python twin; multi-GPU driver)
     NativeProver(params, pk).create_proof(advice_columns, instances, rng) -> bytes       the same per-proof path in C++ (zk_plonk_create_proof)
     MockProver.run(k, cs, fixed, advice, instances, assembly).assert_satisfied()         dev::MockProver (host-only constraint check)
+    NativeMockProver.run(k, cs, fixed, advice, instances, assembly).assert_satisfied()   the same check on the GPU (zk_mock_prover_verify)
 
 verify_proof is not part of the product (verifier side, out of scope); the tests carry their own
 pure-Python verifier as the acceptance check, outside this package.
 """
 from .circuit import ADVICE, FIXED, INSTANCE, Assembly, ConstraintSystem, LookupArgument  # noqa: F401
-from .dev import MockProver, VerifyFailure  # noqa: F401
+from .dev import MockProver, NativeMockProver, VerifyFailure  # noqa: F401
 from .expression import Advice, Constant, Expression, Fixed, Instance  # noqa: F401
 from .keygen import ProvingKey, VerifyingKey, compile_program, keygen  # noqa: F401
 from .prover import create_proof  # noqa: F401

@@ -5,9 +5,12 @@ Host-only and O(rows x constraints) in Python integers: meant for the small circ
 meant for debugging — it bypasses the commitment scheme (and therefore the GPU path) completely."""
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import List, Sequence
 
-from ..fields import R_MOD, fr_int_array
+import numpy as np
+
+from ..fields import R_MOD, fr_int_array, fr_mont_array
 from . import expression as ex
 from .circuit import ADVICE, FIXED, INSTANCE, Assembly, ConstraintSystem
 
@@ -61,6 +64,85 @@ class MockProver:
                         if cols[t][i][row] != cols[t2][i2][rj]:
                             failures.append(f"copy constraint violated: column {j} row {row} != column {cj} row {rj}")
         return failures
+
+    def assert_satisfied(self) -> None:
+        f = self.verify()
+        if f:
+            raise VerifyFailure("; ".join(f[:5]) + (f" (+{len(f) - 5} more)" if len(f) > 5 else ""))
+
+
+MockFailure = namedtuple("MockFailure", "kind index row other_column other_row")   # kind: "gate" | "lookup" | "copy"; other_*: the mapped cell of a copy
+
+
+class NativeMockProver:
+    """MockProver on the GPU: zk_mock_prover_verify (csrc/mockprover.hip) checks the gates, lookups and copy constraints of the witness with HIP kernels over
+    all 2^k rows and returns MockProver.verify()'s failures in MockProver.verify()'s order.  Built from what keygen builds: the Evaluator's ZKQ1 blob
+    (keygen.compile_program; only its custom gates are read), the lookup compressor programs, and Assembly.map_c / map_r as the copy mapping.
+    Gates and lookups are detected through random folds the library draws per call (a failure is missed with probability at most E / |Fr|
+    for E gate polynomials, (m - 1) / |Fr| for a lookup tuple of m expressions); single-phase circuits only, as the native prover."""
+
+    KINDS = ("gate", "lookup", "copy")
+
+    def __init__(self, k: int, cs: ConstraintSystem, fixed: Sequence, advice: Sequence, instances: Sequence[Sequence[int]], assembly: Assembly | None = None,
+                 backend=None):
+        from .._lib import default_backend
+        from .keygen import compile_program, compressor_program
+        self.k, self.n, self.cs, self.assembly = k, 1 << k, cs, assembly
+        self.backend = backend or default_backend()
+        dev = lambda c: not isinstance(c, (np.ndarray, list, tuple))
+        conv = lambda c: c if dev(c) else (np.ascontiguousarray(c).reshape(-1, 4) if isinstance(c, np.ndarray) and c.dtype == np.uint64 else fr_mont_array([int(v) % R_MOD for v in c]))
+        self.fixed = [conv(c) for c in fixed]
+        self.advice = [conv(c) for c in advice]
+        self.instances = [[int(v) for v in c] for c in instances]
+        ek = k
+        while (1 << ek) < self.n * (cs.degree() - 1):                       # EvaluationDomain::new(cs.degree(), k): the blob zk_plonk_pk_build takes
+            ek += 1
+        perm = list(assembly.columns) if assembly is not None else []
+        self.args = dict(k=k, blinding_factors=cs.blinding_factors(), n_fixed=cs.num_fixed_columns, n_advice=cs.num_advice_columns, n_instance=cs.num_instance_columns,
+                         perm_columns=perm, evaluator_blob=compile_program(cs, k, ek).to_blob(),
+                         lookup_input_blobs=[compressor_program(cs, k, lk.input_expressions).to_blob() for lk in cs.lookups],
+                         lookup_table_blobs=[compressor_program(cs, k, lk.table_expressions).to_blob() for lk in cs.lookups],
+                         fixed=self.fixed, advice=self.advice, instances=self.instances,
+                         perm_map_column=assembly.map_c if perm else None, perm_map_row=assembly.map_r if perm else None)
+        self._records, self._counts = None, None
+
+    @classmethod
+    def run(cls, k, cs, fixed, advice, instances, assembly=None, backend=None) -> "NativeMockProver":
+        return cls(k, cs, fixed, advice, instances, assembly, backend)
+
+    def _check(self, cap: int):
+        recs, counts = self.backend.mock_prover_verify(cap=cap, **self.args)
+        return [MockFailure(self.KINDS[r[0]], *r[1:]) for r in recs], counts
+
+    def failures(self, cap: int | None = None) -> List[MockFailure]:
+        """the structured records: all of them, or the first `cap` (one device check per call with a cap)"""
+        if cap is not None:
+            return self._check(cap)[0]
+        if self._records is None:
+            recs, counts = self._check(4096)
+            if sum(counts) > len(recs):
+                recs, counts = self._check(sum(counts))
+            self._records, self._counts = recs, counts
+        return self._records
+
+    @property
+    def counts(self):
+        """(gate, lookup, copy) failures, exact"""
+        if self._counts is None:
+            self.failures()
+        return self._counts
+
+    def verify(self) -> List[str]:
+        """MockProver.verify()'s strings, one per record, in its order"""
+        out = []
+        for f in self.failures():
+            if f.kind == "gate":
+                out.append(f"gate {f.index} not satisfied on row {f.row}")
+            elif f.kind == "lookup":
+                out.append(f"lookup {f.index}: input of row {f.row} is not in the table")
+            else:
+                out.append(f"copy constraint violated: column {f.index} row {f.row} != column {f.other_column} row {f.other_row}")
+        return out
 
     def assert_satisfied(self) -> None:
         f = self.verify()

@@ -118,12 +118,16 @@ def compile_program(cs: ConstraintSystem, k: int, extended_k: int) -> ev.Program
                       perm_columns=list(cs.permutation_columns), custom_gates=gb.graph, lookups=lookups)
 
 
-def _compressor(cs: ConstraintSystem, k: int, exprs, be: Backend) -> ev.Evaluator:
-    """lookup::Argument::commit_permuted's compress_expressions as a program over the Lagrange columns."""
+def compressor_program(cs: ConstraintSystem, k: int, exprs) -> ev.Program:
+    """lookup::Argument::commit_permuted's compress_expressions as a program over the Lagrange columns (extended_k = k)."""
     gb = GraphBuilder()
     ps = [gb.add_expression(e) for e in exprs]
     gb.add_calculation(ev.HORNER, ev.vs(ev.CONSTANT, 0), ps, ev.vs(ev.THETA))
-    return ev.Evaluator(ev.expression_program(k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, 0, gb.graph), backend=be)
+    return ev.expression_program(k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, 0, gb.graph)
+
+
+def _compressor(cs: ConstraintSystem, k: int, exprs, be: Backend) -> ev.Evaluator:
+    return ev.Evaluator(compressor_program(cs, k, exprs), backend=be)
 
 
 def _as_mont(col, n) -> np.ndarray:
