@@ -74,22 +74,24 @@ def build_program(orc, pyref, k, cs_degree, n_fixed, n_advice, n_instance, n_cha
                       blinding_factors=5, cs_degree=cs_degree, perm_columns=perm_columns, custom_gates=custom, lookups=lookups)
 
 
-def rand_cols(pc_mod, orc, pyref, count, size, seed):
-    return [pc_mod.rand_fr(orc, pyref, size, seed + 7 * i) for i in range(count)]
+def rand_cols(pc_mod, orc, pyref, count, size, seed, kind="uniform"):
+    return [pc_mod.column(orc, pyref, size, seed + 7 * i, kind) for i in range(count)]
 
 
-def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_kernels=False):
+def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_kernels=False, kind="uniform"):
+    """kind: every column (fixed, advice, instance, sigma cosets, grand products, lookup columns, l0 / l_last / l_active_row) is a structured column of that kind
+    (parity_cases.structured_fr) in place of a uniform one; the challenges stay uniform"""
     size = 1 << prog.extended_k
     chunk = prog.cs_degree - 2
     n_sets = (len(prog.perm_columns) + chunk - 1) // chunk if prog.perm_columns else 0
     nl = len(prog.lookups)
-    cols = dict(fixed=rand_cols(pc_mod, orc, pyref, prog.n_fixed, size, seed), advice=rand_cols(pc_mod, orc, pyref, prog.n_advice, size, seed + 100),
-                instance=rand_cols(pc_mod, orc, pyref, prog.n_instance, size, seed + 200),
-                perm_cosets=rand_cols(pc_mod, orc, pyref, len(prog.perm_columns), size, seed + 300),
-                perm_products=rand_cols(pc_mod, orc, pyref, n_sets, size, seed + 400),
-                lookup_product=rand_cols(pc_mod, orc, pyref, nl, size, seed + 500), lookup_input=rand_cols(pc_mod, orc, pyref, nl, size, seed + 600),
-                lookup_table=rand_cols(pc_mod, orc, pyref, nl, size, seed + 700))
-    l0, l_last, l_active = rand_cols(pc_mod, orc, pyref, 3, size, seed + 800)
+    cols = dict(fixed=rand_cols(pc_mod, orc, pyref, prog.n_fixed, size, seed, kind), advice=rand_cols(pc_mod, orc, pyref, prog.n_advice, size, seed + 100, kind),
+                instance=rand_cols(pc_mod, orc, pyref, prog.n_instance, size, seed + 200, kind),
+                perm_cosets=rand_cols(pc_mod, orc, pyref, len(prog.perm_columns), size, seed + 300, kind),
+                perm_products=rand_cols(pc_mod, orc, pyref, n_sets, size, seed + 400, kind),
+                lookup_product=rand_cols(pc_mod, orc, pyref, nl, size, seed + 500, kind), lookup_input=rand_cols(pc_mod, orc, pyref, nl, size, seed + 600, kind),
+                lookup_table=rand_cols(pc_mod, orc, pyref, nl, size, seed + 700, kind))
+    l0, l_last, l_active = rand_cols(pc_mod, orc, pyref, 3, size, seed + 800, kind)
     chal = pc_mod.rand_fr(orc, pyref, max(prog.n_challenges, 1), seed + 900)[: prog.n_challenges]
     beta, gamma, theta, y = pc_mod.rand_fr(orc, pyref, 4, seed + 901)
     want = orc.evaluate_h(prog.to_blob(), cols["fixed"], cols["advice"], cols["instance"], l0, l_last, l_active, cols["perm_cosets"],

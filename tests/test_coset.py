@@ -6,9 +6,10 @@ import pytest
 import parity_cases as pc
 
 
-def _check(be, orc, pyref, k, e, seed):
+def _check(be, orc, pyref, k, e, seed, kinds=("uniform",)):
+    """kinds: the three polynomials are columns of kind kinds[i % len(kinds)]"""
     n, ek = 1 << k, k + e
-    polys = [pc.rand_fr(orc, pyref, n, seed + i) for i in range(3)]
+    polys = [pc.column(orc, pyref, n, seed + i, kinds[i % len(kinds)]) for i in range(3)]
     d = [be.to_device(p) for p in polys]
     ext = [be.alloc((n << e) * 32) for _ in polys]
     be.coeff_to_extended_batch_dev(d, ext, k, ek)
@@ -21,6 +22,9 @@ def _check(be, orc, pyref, k, e, seed):
     out = be.alloc((n << e) * 32)
     be.fr_interleave_dev([cos[j][1] for j in range(1 << e)], n, out)
     assert (out.download((n << e, 4)) == full[1]).all()
+    for b in d + ext + [c for row in cos for c in row] + [out]:
+        b.free()
+    return polys, full
 
 
 @pytest.mark.parametrize("k,e", [(4, 1), (5, 2), (6, 3), (7, 2), (8, 1), (9, 3)])      # above the fixture's tile (2^6) a coset transform takes its pre-scaling from ONE table (ntt_coset_table)
@@ -54,11 +58,11 @@ def test_gpu_cosets(gpu, orc, pyref, k, e):
     _check(gpu, orc, pyref, k, e, seed=k)
 
 
-def _check_pieces(be, orc, pyref, k, e, q, seed):
+def _check_pieces(be, orc, pyref, k, e, q, seed, kinds=("uniform",)):
     """random pieces h_0 .. h_{q-1} -> the numerator h * (X^n - 1) on every coset (coset values of the pieces, combined with s_j^i and s_j - 1 in Python-derived scalars) ->
     zk_cosets_to_pieces_dev on cosets 0 .. q-1 must return the pieces; the extended route over ALL cosets (interleave, divide_by_vanishing_poly, extended_to_coeff) must too"""
     n, ek, R = 1 << k, k + e, pyref.R
-    pieces = [pc.rand_fr(orc, pyref, n, seed + i) for i in range(q)]
+    pieces = [pc.column(orc, pyref, n, seed + i, kinds[i % len(kinds)]) for i in range(q)]
     d = [be.to_device(p) for p in pieces]
     zn, won = pow(pyref.ZETA, n, R), pow(pyref.omega(ek), n, R)
     numer = []

@@ -57,9 +57,10 @@ def test_oracle_lookup_product_matches_definition(orc, pyref):
     assert got == want + blind
 
 
-def _check_backend(be, orc, pyref, k, count, seed, bf=5):
+def _check_backend(be, orc, pyref, k, count, seed, bf=5, inputs=None):
+    """inputs: (values, sigmas, beta, gamma) in place of the uniform ones — the structured cases place zero denominators, zero numerators and unit fractions in them"""
     n = 1 << k
-    vals, sig, beta, gamma = _inputs(orc, pyref, k, count, seed)
+    vals, sig, beta, gamma = inputs if inputs is not None else _inputs(orc, pyref, k, count, seed)
     blind = pc.rand_fr(orc, pyref, bf, seed + 7)
     z0 = pc.rand_fr(orc, pyref, 1, seed + 8)[0]
     dstart = orc.fr_from_ints([pow(pyref.DELTA, 3, pyref.R)])[0]
@@ -80,6 +81,7 @@ def _check_backend(be, orc, pyref, k, count, seed, bf=5):
         assert (zz.download((n, 4)) == orc.lookup_product(q[0], q[1], q[2], q[3], k, beta, gamma, b)).all()
     for d in dv + ds + [dz] + zs:
         d.free()
+    return want, want_l
 
 
 @pytest.mark.parametrize("k,count", [(3, 1), (5, 3), (9, 2), (11, 2), (12, 4)])
@@ -87,21 +89,30 @@ def test_emulated_grand_products(emu, orc, pyref, k, count):
     _check_backend(emu, orc, pyref, k, count, seed=10 * k + count)
 
 
-@pytest.mark.parametrize("k", [5, 11, 12])     # all sets in one launch sequence; 5: partial scan spans, 11: one span per column, 12: two
-def test_permutation_commit_chains_sets(emu, orc, pyref, k):
-    """permutation_commit(): z of set s starts at the last unblinded value of set s-1, delta powers continue."""
+def _check_commit(be, orc, pyref, k, inputs=None):
+    """permutation_commit(): z of set s starts at the last unblinded value of set s-1, delta powers continue.  inputs: as _check_backend (five columns)."""
     cs_degree, ncols, bf = 4, 5, 5
     n = 1 << k
-    vals, sig, beta, gamma = _inputs(orc, pyref, k, ncols, 21)
+    vals, sig, beta, gamma = inputs if inputs is not None else _inputs(orc, pyref, k, ncols, 21)
     blind = [pc.rand_fr(orc, pyref, bf, 30 + s) for s in range(3)]
-    dv, ds = [emu.to_device(c) for c in vals], [emu.to_device(c) for c in sig]
-    zs = z.permutation.permutation_commit(dv, ds, k, cs_degree, beta, gamma, blind, backend=emu)
+    dv, ds = [be.to_device(c) for c in vals], [be.to_device(c) for c in sig]
+    zs = z.permutation.permutation_commit(dv, ds, k, cs_degree, beta, gamma, blind, backend=be)
     assert len(zs) == 3
     last = orc.fr_from_ints([1])[0]
+    got = []
     for s, lo in enumerate(range(0, ncols, cs_degree - 2)):
         want, last = orc.permutation_product(vals[lo:lo + 2], sig[lo:lo + 2], k, beta, gamma,
                                              orc.fr_from_ints([pow(pyref.DELTA, lo, pyref.R)])[0], last, blind[s])
-        assert (zs[s].download((n, 4)) == want).all(), s
+        got.append(zs[s].download((n, 4)))
+        assert (got[-1] == want).all(), s
+    for d in dv + ds + zs:
+        d.free()
+    return got
+
+
+@pytest.mark.parametrize("k", [5, 11, 12])     # all sets in one launch sequence; 5: partial scan spans, 11: one span per column, 12: two
+def test_permutation_commit_chains_sets(emu, orc, pyref, k):
+    _check_commit(emu, orc, pyref, k)
 
 
 @pytest.mark.gpu

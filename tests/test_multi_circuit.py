@@ -312,9 +312,10 @@ def test_errors_emulated(emu, orc):
 
 
 # ---- the accumulate mode of the quotient on its own ------------------------------------------------------------------------------------------------------
-def _acc_kernel(be, k, circuit, seed):
+def _acc_kernel(be, k, circuit, seed, cancel=False, kind="uniform", orc=None):
     """for random columns, every route and part: zk_quotient_run_acc_dev gives prev * y^E + N, N from the non-accumulating entry point, prev random, E counted from
-    the constraint system; checked with host big-int arithmetic"""
+    the constraint system; checked with host big-int arithmetic.  cancel: one more accumulating run per route with prev = -N * y^(-E), which must leave exactly 0 (all limbs) on
+    every row; kind: the columns are structured ones (parity_cases.structured_fr) instead of uniform"""
     cs, fixed, asm = circuit
     params, pk, _ = _setup(be, k, cs, fixed, asm, piece_cosets=False)
     prog = pk.evaluator.handle
@@ -331,6 +332,11 @@ def _acc_kernel(be, k, circuit, seed):
     host_l = [rand_fr_array(rng, size) for _ in range(3)]
     beta, gamma, theta, y = (fr_mont(int(v)) for v in rng.integers(1, 1 << 62, size=4))
     yE = pow(fr_int_array(y.reshape(1, 4))[0], E, R_MOD)
+    if kind != "uniform":
+        import parity_cases as pc
+        import pyref
+        host = {key: [pc.structured_fr(orc, pyref, size, kind, seed + 10 * i + j) for j in range(c)] for i, (key, c) in enumerate(counts.items())}
+        host_l = [pc.structured_fr(orc, pyref, size, kind, seed + 100 + j) for j in range(3)]
     split = be.quotient_program_split(prog)["low_cosets"]
     assert split == 2                                                # (the programs here all have a degree split: every part is covered)
 
@@ -344,6 +350,13 @@ def _acc_kernel(be, k, circuit, seed):
             be.quotient_run_dev(prog, **{key: dev[key] for key in dev}, l0=dl[0], l_last=dl[1], l_active_row=dl[2], challenges=[], beta=beta, gamma=gamma,
                                 theta=theta, y=y, out=o, accumulate=acc, **kw)
             outs.append(o.download((out_rows, 4)))
+            o.free()
+        if cancel:
+            yEi = pow(yE, -1, R_MOD)
+            o = be.to_device(fr_mont_array([(-n_ * yEi) % R_MOD for n_ in fr_int_array(outs[0])]))
+            be.quotient_run_dev(prog, **{key: dev[key] for key in dev}, l0=dl[0], l_last=dl[1], l_active_row=dl[2], challenges=[], beta=beta, gamma=gamma,
+                                theta=theta, y=y, out=o, accumulate=True, **kw)
+            assert not o.download((out_rows, 4)).any(), ("prev * y^E + N must be the canonical zero on every row", kw)
             o.free()
         for v in dev.values():
             for d in v:
