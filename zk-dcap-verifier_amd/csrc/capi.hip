@@ -21,8 +21,6 @@ int permutation_product(zk_ctx* ctx, const void* const* values, const void* cons
                         const void* delta_start, const void* z_init, const void* blinding, uint32_t bf, void* d_z, void* h_last_z);
 int lookup_product(zk_ctx* ctx, const void* cin, const void* ctab, const void* pin, const void* ptab, uint32_t k, const void* beta, const void* gamma,
                    const void* blinding, uint32_t bf, void* d_z);
-int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
-                            const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs);
 int permutation_product_circuits(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, size_t n_circuits, uint32_t chunk_len, uint32_t k,
                                  const void* beta, const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs);
 int lookup_product_batch(zk_ctx* ctx, const void* const* cols4, size_t count, uint32_t k, const void* beta, const void* gamma, const void* blinding,
@@ -129,8 +127,8 @@ long zk_test_live_device_allocs(void) { return emu_live_device_allocs.load(); }
 }  // extern "C"
 #endif
 
-void zk_internal_plonk_ctx_destroyed(zk_ctx* ctx);   // prover.hip
-// prover.hip is a client of the public ABI and does not see zk_ctx's members: its own argument errors reach zk_last_error through this
+void zk_internal_plonk_ctx_destroyed(zk_ctx* ctx);   // pk.hip
+// prover.hip and pk.hip are clients of the public ABI and do not see zk_ctx's members: its own argument errors reach zk_last_error through this
 int zk_internal_fail(zk_ctx* ctx, int code, const char* msg) { return ctx ? ctx->fail(code, "%s", msg) : code; }
 #define LOCK std::lock_guard<std::mutex> lk__(ctx->mu)
 #define NEED_CTX if (!ctx) return ZK_ERR_ARG
@@ -241,7 +239,7 @@ void zk_ctx_destroy(zk_ctx* ctx) ZK_ABI_TRY {
     zk_ctx* helper;
     { LOCK; helper = ctx->helper; ctx->helper = nullptr; }
     if (helper) zk_ctx_destroy(helper);
-    zk_internal_plonk_ctx_destroyed(ctx);       // proving keys built on / shared to this context (prover.hip)
+    zk_internal_plonk_ctx_destroyed(ctx);       // proving keys built on / shared to this context (pk.hip)
     (void)zk_plonk_trim(ctx);                   // device buffers zk_plonk_create_proof kept for reuse on this context (a later context at the same address must not inherit them)
     {
         LOCK;
@@ -488,10 +486,10 @@ int zk_lookup_product_dev(zk_ctx* ctx, const void* cin, const void* ctab, const 
 
 int zk_permutation_product_all_dev(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t n_columns, uint32_t chunk_len, uint32_t k,
                                    const void* beta, const void* gamma, const void* blinding, uint32_t blinding_factors, void* const* z_devs) ZK_ABI_TRY {
-    ENTER; return permutation_product_all(ctx, values, sigmas, n_columns, chunk_len, k, beta, gamma, blinding, blinding_factors, z_devs);
+    ENTER; return permutation_product_circuits(ctx, values, sigmas, n_columns, 1, chunk_len, k, beta, gamma, blinding, blinding_factors, z_devs);
 } ZK_ABI_CATCH(ctx)
 }  // extern "C"
-// prover.hip (an m-circuit proof): the permutation arguments of all circuits in one launch sequence (zk_permutation_product_all_dev per circuit, batched)
+// prover.hip (a proof over m >= 1 circuits): the permutation arguments of all circuits in one launch sequence (zk_permutation_product_all_dev per circuit, batched)
 int zk_internal_permutation_products(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t n_columns, size_t n_circuits, uint32_t chunk_len, uint32_t k,
                                      const void* beta, const void* gamma, const void* blinding, uint32_t blinding_factors, void* const* z_devs) {
     ENTER; return permutation_product_circuits(ctx, values, sigmas, n_columns, n_circuits, chunk_len, k, beta, gamma, blinding, blinding_factors, z_devs);

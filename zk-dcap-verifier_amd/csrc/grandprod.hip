@@ -294,22 +294,8 @@ int permutation_product(zk_ctx* ctx, const void* const* values, const void* cons
     return gp_permutation(ctx, values, sigmas, count, (uint32_t)count, k, beta, gamma, gp_rd(delta_start), gp_rd(z_init), blinding, bf, &d_z, h_last_z);
 }
 
-// All column sets of the permutation argument in one launch sequence.  d_zs: n_sets outputs; blinding: n_sets x bf x 32 B.
-int permutation_product_all(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, uint32_t chunk_len, uint32_t k, const void* beta,
-                            const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs) {
-    if (m == 0) return ZK_OK;
-    if (!values || !sigmas || !beta || !gamma || !d_zs || (bf && !blinding) || chunk_len == 0) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null argument");
-    if (chunk_len > (uint32_t)GP_MAX_COLS) return ctx->fail(ZK_ERR_LIMIT, "zk_permutation_product_all_dev: %u columns per set (max %d)", chunk_len, GP_MAX_COLS);
-    if (k > 27 || k < 1) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: k = %u out of range", k);
-    const uint32_t n = 1u << k;
-    if (bf + 2 >= n) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: blinding_factors too large");
-    for (size_t j = 0; j < m; j++)
-        if (!values[j] || !sigmas[j]) return ctx->fail(ZK_ERR_ARG, "zk_permutation_product_all_dev: null column %zu", j);
-    return gp_permutation(ctx, values, sigmas, m, chunk_len, k, beta, gamma, Fr::one(), Fr::one(), blinding, bf, d_zs, nullptr);
-}
-
 // The permutation arguments of several circuits that share a key (one proof over n_circuits circuits): values = n_circuits x m columns, circuit-major; sigmas = m;
-// d_zs = n_circuits x n_sets, blinding likewise.  One launch sequence for all of them; every circuit's sets chain on their own, exactly as permutation_product_all per circuit.
+// d_zs = n_circuits x n_sets, blinding likewise.  One launch sequence for all of them; every circuit's sets chain on their own (n_circuits = 1: zk_permutation_product_all_dev).
 int permutation_product_circuits(zk_ctx* ctx, const void* const* values, const void* const* sigmas, size_t m, size_t n_circuits, uint32_t chunk_len, uint32_t k,
                                  const void* beta, const void* gamma, const void* blinding, uint32_t bf, void* const* d_zs) {
     if (m == 0 || n_circuits == 0) return ZK_OK;

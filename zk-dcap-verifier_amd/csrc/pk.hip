@@ -1,0 +1,275 @@
+// ---- the proving key as a library object (zk_plonk_pk_build / share / release / prove) -------------------------------------------------------------------------
+// The device half of keygen_pk, written — like create_proof (prover.hip) — as a CLIENT of the public entry points: upload the Lagrange columns, lagrange_to_coeff,
+// coeff_to_extended, l0 / l_last / l_active_row, load the ZKQ1 programs.  One PkMem per key per process (columns + the host arrays the descriptor points into);
+// every holding context has a PkHandle with its own program handles (zk_quotient_program_share) and SRS handles.
+#include <string.h>
+#include <map>
+#include <mutex>
+#include <vector>
+#include "field.cuh"
+#include "../../include/zkmi355.h"
+#include "abi_guard.h"
+#include "plonk_shared.h"
+
+using namespace zk;
+
+#define PK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
+
+namespace {
+struct PkMem {
+    std::vector<void*> owned;                                         // device allocations, freed by whoever drops the last handle
+    std::vector<const void*> fixed_values, fixed_polys, fixed_cosets, sigma_values, sigma_polys, sigma_cosets;
+    void* l[3] = {nullptr, nullptr, nullptr};
+    std::vector<const void*> coset_fixed, coset_sigma, coset_l;      // a sharded key: [this rank's cosets][columns], n values each
+    std::vector<uint32_t> perm_columns, advice_queries, fixed_queries, table_key;
+    uint8_t transcript_repr[32];
+    int holders = 0;
+};
+struct PkHandle {
+    PkMem* mem = nullptr;
+    zk_plonk_pk_desc desc;
+    uint64_t program = 0;
+    std::vector<uint64_t> in_prog, tab_prog;
+    int in_use = 0;              // zk_plonk_prove calls running on this handle (g_pk_mu)
+    bool released = false;       // zk_plonk_pk_release / zk_ctx_destroy arrived meanwhile: the last of those calls drops the handle
+};
+std::mutex g_pk_mu;
+std::map<std::pair<zk_ctx*, uint64_t>, PkHandle*> g_pk_handles;
+uint64_t g_pk_next = 1;
+
+void pk_fill_desc(PkHandle* h, const zk_plonk_pk_desc& shape, uint64_t srs_g, uint64_t srs_g_lagrange) {
+    PkMem* m = h->mem;
+    zk_plonk_pk_desc& d = h->desc;
+    d = shape;
+    d.perm_columns = m->perm_columns.data(); d.advice_queries = m->advice_queries.data(); d.fixed_queries = m->fixed_queries.data();
+    d.srs_g = srs_g; d.srs_g_lagrange = srs_g_lagrange; d.program = h->program;
+    d.lookup_input_programs = h->in_prog.data(); d.lookup_table_programs = h->tab_prog.data(); d.lookup_table_key = m->table_key.data();
+    d.fixed_values = m->fixed_values.data(); d.fixed_polys = m->fixed_polys.data(); d.fixed_cosets = m->fixed_cosets.data();
+    d.sigma_values = m->sigma_values.data(); d.sigma_polys = m->sigma_polys.data(); d.sigma_cosets = m->sigma_cosets.data();
+    d.l0 = m->l[0]; d.l_last = m->l[1]; d.l_active_row = m->l[2];
+    d.coset_fixed = m->coset_fixed.data(); d.coset_sigma = m->coset_sigma.data(); d.coset_l = m->coset_l.data();
+    d.transcript_repr = m->transcript_repr;
+}
+void pk_drop(zk_ctx* ctx, PkHandle* h) {                              // g_pk_mu held
+    if (h->program) (void)zk_quotient_program_release(ctx, h->program);
+    for (uint64_t p : h->in_prog) if (p) (void)zk_quotient_program_release(ctx, p);
+    for (uint64_t p : h->tab_prog) if (p) (void)zk_quotient_program_release(ctx, p);
+    if (h->mem && --h->mem->holders == 0) {
+        for (void* p : h->mem->owned) (void)zk_dev_free(ctx, p);
+        delete h->mem;
+    }
+    delete h;
+}
+}  // namespace
+
+extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
+    if (!ctx || !host || !pk) return ZK_ERR_ARG;
+    if (host->struct_size != sizeof(zk_plonk_pk_host))
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build: zk_plonk_pk_host.struct_size %u, expected %zu (ABI version %u)", host->struct_size, sizeof(zk_plonk_pk_host), ZK_ABI_VERSION);
+    const uint32_t k = host->k, L = host->n_lookups;
+    if (k < 1 || k > 27 || host->cs_degree < 3 || host->transcript > 2 || host->draw_schedule != 1 || !host->transcript_repr || !host->evaluator_zkq1) return ZK_ERR_ARG;
+    if ((host->n_fixed && !host->fixed_values) || (host->n_perm_columns && (!host->sigma_values || !host->perm_columns)) || (host->n_advice_queries && !host->advice_queries) ||
+        (host->n_fixed_queries && !host->fixed_queries) ||
+        (L && (!host->lookup_input_zkq1 || !host->lookup_input_zkq1_len || !host->lookup_table_zkq1 || !host->lookup_table_zkq1_len || !host->lookup_table_key)))
+        return ZK_ERR_ARG;
+    const size_t n = (size_t)1 << k, col_bytes = n * 32;
+    if ((size_t)host->blinding_factors + 2 >= n) return ZK_ERR_ARG;
+    uint32_t ek = k;                                                  // EvaluationDomain::new(j, k): the smallest extended domain that holds a quotient of degree (j - 1) n
+    while (((size_t)1 << ek) < n * (host->cs_degree - 1)) ek++;
+    if (ek > 27) return ZK_ERR_LIMIT;
+    const size_t ext_bytes = (size_t)32 << ek;
+    PkHandle* h = new PkHandle();
+    struct Undo { zk_ctx* ctx; PkHandle* h; ~Undo() { if (h) { std::lock_guard<std::mutex> lk(g_pk_mu); pk_drop(ctx, h); } } } undo{ctx, h};      // every way out but the last line drops the half-built key
+    h->mem = new PkMem();
+    h->mem->holders = 1;
+    PkMem* m = h->mem;
+    auto alloc = [&](size_t bytes) -> void* {
+        m->owned.reserve(m->owned.size() + 1);                         // (the slot first: a buffer is never allocated without an owner to free it)
+        void* p = nullptr;
+        if (zk_dev_alloc(ctx, bytes, &p) != ZK_OK) return nullptr;
+        m->owned.push_back(p);
+        return p;
+    };
+    // values -> (values, polys, cosets); `src` are host columns, or device columns that are borrowed as they are
+    // a sharded key keeps only the cosets this rank's quotient units live on (the unit rule of zk_plonk_pk_desc), n values per column
+    const uint32_t world = host->shard_world > 1 ? host->shard_world : 1;
+    if (world > 1 && (host->shard_rank >= world || n % world || !host->allgather)) return ZK_ERR_ARG;
+    std::vector<uint32_t> my_cosets = quotient_units(world, host->shard_rank, k, ek).my_cosets;
+    // a single GPU needs h(X)'s numerator on cs_degree - 1 cosets only (zk_cosets_to_pieces_dev): when that is fewer than the 2^(ek - k) of the extended domain the key
+    // keeps cosets 0 .. cs_degree-2, n values per column, and no extended form at all (tunable "quot_piece_cosets", default on)
+    bool whole_domain = world == 1;
+    if (world == 1 && host->cs_degree - 1 < (1u << (ek - k)) && host->cs_degree - 1 <= 8) {
+        int on = 1;
+        (void)zk_tune_get(ctx, "quot_piece_cosets", &on);
+        if (on) { whole_domain = false; for (uint32_t j = 0; j + 1 < host->cs_degree; j++) my_cosets.push_back(j); }
+    }
+    // coeffs -> extended cosets (`cosets`) or the cosets this key keeps (`by_coset`, [coset][column])
+    auto to_cosets = [&](std::vector<void*>& pl, std::vector<const void*>& cosets, std::vector<const void*>& by_coset) -> int {
+        const size_t count = pl.size();
+        if (whole_domain) {
+            std::vector<void*> cs(count);
+            for (auto& c : cs) { c = alloc(ext_bytes); if (!c) return ZK_ERR_HIP; }
+            if (count) PK(zk_coeff_to_extended_batch_dev(ctx, (const void* const*)pl.data(), cs.data(), count, k, ek));
+            cosets.assign(cs.begin(), cs.end());
+            return ZK_OK;
+        }
+        for (uint32_t j : my_cosets) {
+            std::vector<void*> cs(count);
+            for (auto& c : cs) { c = alloc(col_bytes); if (!c) return ZK_ERR_HIP; }
+            if (count) PK(zk_coeff_to_coset_batch_dev(ctx, (const void* const*)pl.data(), cs.data(), count, k, ek, j));
+            by_coset.insert(by_coset.end(), cs.begin(), cs.end());
+        }
+        return ZK_OK;
+    };
+    auto three_forms = [&](const void* const* src, size_t count, bool on_device, std::vector<const void*>& values, std::vector<const void*>& polys, std::vector<const void*>& cosets,
+                           std::vector<const void*>& by_coset) -> int {
+        std::vector<void*> dst, pl;
+        std::vector<const void*> hs;
+        for (size_t i = 0; i < count; i++) {
+            if (!src[i]) return ZK_ERR_ARG;
+            if (on_device) values.push_back(src[i]);
+            else { void* v = alloc(col_bytes); if (!v) return ZK_ERR_HIP; values.push_back(v); dst.push_back(v); hs.push_back(src[i]); }
+            void* p = alloc(col_bytes);
+            if (!p) return ZK_ERR_HIP;
+            pl.push_back(p);
+        }
+        if (!dst.empty()) PK(zk_dev_upload_batch(ctx, dst.data(), hs.data(), dst.size(), col_bytes));
+        for (size_t i = 0; i < count; i++) PK(zk_dev_copy(ctx, pl[i], values[i], col_bytes));
+        if (count) PK(zk_lagrange_to_coeff_batch_dev(ctx, pl.data(), count, k));
+        polys.assign(pl.begin(), pl.end());
+        return to_cosets(pl, cosets, by_coset);
+    };
+    int rc = three_forms(host->fixed_values, host->n_fixed, host->values_on_device != 0, m->fixed_values, m->fixed_polys, m->fixed_cosets, m->coset_fixed);
+    if (!rc) rc = three_forms(host->sigma_values, host->n_perm_columns, host->values_on_device != 0, m->sigma_values, m->sigma_polys, m->sigma_cosets, m->coset_sigma);
+    if (rc) return rc;
+    {   // l0 = [row 0], l_last = [row n - bf - 1], l_active_row = [rows below it]: Lagrange columns -> extended cosets (keygen.rs)
+        const size_t last = n - host->blinding_factors - 1;
+        std::vector<uint64_t> col(3 * n * 4, 0);
+        const u256 one = Fr::one();
+        memcpy(&col[0], one.v, 32);
+        memcpy(&col[(n + last) * 4], one.v, 32);
+        for (size_t i = 0; i < last; i++) memcpy(&col[(2 * n + i) * 4], one.v, 32);
+        struct Tmp { zk_ctx* ctx; std::vector<void*> v; ~Tmp() { for (void* p : v) if (p) (void)zk_dev_free(ctx, p); } } t{ctx, std::vector<void*>(3, nullptr)};
+        std::vector<void*>& tmp = t.v;
+        const void* hs[3];
+        for (int i = 0; i < 3; i++) {
+            if (zk_dev_alloc(ctx, col_bytes, &tmp[i]) != ZK_OK) return ZK_ERR_HIP;
+            hs[i] = &col[(size_t)i * n * 4];
+        }
+        rc = zk_dev_upload_batch(ctx, tmp.data(), hs, 3, col_bytes);
+        if (!rc) rc = zk_lagrange_to_coeff_batch_dev(ctx, tmp.data(), 3, k);
+        std::vector<const void*> ext;
+        if (!rc) rc = to_cosets(tmp, ext, m->coset_l);
+        if (rc) return rc;
+        for (int i = 0; i < 3 && whole_domain; i++) m->l[i] = (void*)ext[i];
+    }
+    rc = zk_quotient_program_load(ctx, host->evaluator_zkq1, host->evaluator_zkq1_len, &h->program);
+    h->in_prog.assign(L, 0); h->tab_prog.assign(L, 0);
+    for (uint32_t l = 0; l < L && !rc; l++) {
+        rc = zk_quotient_program_load(ctx, host->lookup_input_zkq1[l], host->lookup_input_zkq1_len[l], &h->in_prog[l]);
+        if (!rc) rc = zk_quotient_program_load(ctx, host->lookup_table_zkq1[l], host->lookup_table_zkq1_len[l], &h->tab_prog[l]);
+    }
+    if (rc) return rc;
+    m->perm_columns.assign(host->perm_columns, host->perm_columns + 2 * (size_t)host->n_perm_columns);
+    m->advice_queries.assign(host->advice_queries, host->advice_queries + 2 * (size_t)host->n_advice_queries);
+    m->fixed_queries.assign(host->fixed_queries, host->fixed_queries + 2 * (size_t)host->n_fixed_queries);
+    m->table_key.assign(host->lookup_table_key, host->lookup_table_key + L);
+    m->perm_columns.push_back(0); m->advice_queries.push_back(0); m->fixed_queries.push_back(0); m->table_key.push_back(0);      // .data() of an empty vector may be null: the prover refuses null arrays
+    h->in_prog.push_back(0); h->tab_prog.push_back(0);
+    for (auto* v : {&m->fixed_values, &m->fixed_polys, &m->fixed_cosets, &m->sigma_values, &m->sigma_polys, &m->sigma_cosets, &m->coset_fixed, &m->coset_sigma, &m->coset_l}) v->push_back(nullptr);
+    memcpy(m->transcript_repr, host->transcript_repr, 32);
+    zk_plonk_pk_desc shape;
+    ZK_STRUCT_INIT(shape);
+    shape.k = k; shape.extended_k = ek; shape.cs_degree = host->cs_degree; shape.blinding_factors = host->blinding_factors;
+    shape.n_fixed = host->n_fixed; shape.n_advice = host->n_advice; shape.n_instance = host->n_instance; shape.n_lookups = L; shape.n_perm_columns = host->n_perm_columns;
+    shape.n_advice_queries = host->n_advice_queries; shape.n_fixed_queries = host->n_fixed_queries;
+    shape.transcript = host->transcript; shape.draw_schedule = host->draw_schedule;
+    shape.shard_world = host->shard_world; shape.shard_rank = host->shard_rank; shape.allgather = host->allgather; shape.allgather_user = host->allgather_user;
+    pk_fill_desc(h, shape, srs_g, srs_g_lagrange);
+    {
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        g_pk_handles[{ctx, g_pk_next}] = h;
+        *pk = g_pk_next++;
+    }
+    undo.h = nullptr;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_pk_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_pk, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
+    if (!ctx || !owner || !pk) return ZK_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_pk_handles.find({owner, owner_pk});
+    if (it == g_pk_handles.end()) return ZK_ERR_ARG;
+    const PkHandle* src = it->second;
+    PkHandle* h = new PkHandle();
+    struct Undo { zk_ctx* ctx; PkHandle* h; ~Undo() { if (h) pk_drop(ctx, h); } } undo{ctx, h};      // (g_pk_mu is held for the whole function)
+    h->mem = src->mem;
+    h->mem->holders++;
+    const size_t L = src->desc.n_lookups;
+    h->in_prog.assign(L + 1, 0); h->tab_prog.assign(L + 1, 0);
+    int rc = zk_quotient_program_share(ctx, owner, src->program, &h->program);                  // (refuses contexts on different devices)
+    for (size_t l = 0; l < L && !rc; l++) {
+        rc = zk_quotient_program_share(ctx, owner, src->in_prog[l], &h->in_prog[l]);
+        if (!rc) rc = zk_quotient_program_share(ctx, owner, src->tab_prog[l], &h->tab_prog[l]);
+    }
+    if (rc) return rc;
+    pk_fill_desc(h, src->desc, srs_g, srs_g_lagrange);
+    g_pk_handles[{ctx, g_pk_next}] = h;
+    *pk = g_pk_next++;
+    undo.h = nullptr;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_pk_release(zk_ctx* ctx, uint64_t pk) ZK_ABI_TRY {
+    if (!ctx) return ZK_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_pk_handles.find({ctx, pk});
+    if (it == g_pk_handles.end()) return ZK_ERR_ARG;
+    if (it->second->in_use) it->second->released = true;             // a proof is running through this handle on another thread: it drops the handle when it returns
+    else pk_drop(ctx, it->second);
+    g_pk_handles.erase(it);
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_pk_descriptor(zk_ctx* ctx, uint64_t pk, const zk_plonk_pk_desc** desc) ZK_ABI_TRY {
+    if (!ctx || !desc) return ZK_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_pk_handles.find({ctx, pk});
+    if (it == g_pk_handles.end()) return ZK_ERR_ARG;
+    *desc = &it->second->desc;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+// zk_plonk_prove / zk_plonk_prove_multi: the handle (descriptor, programs, its share of the columns) stays alive for the whole proof whatever other threads release meanwhile
+static int prove_with_key(const char* fn, zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
+                          const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!ctx) return ZK_ERR_ARG;
+    PkHandle* h = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        auto it = g_pk_handles.find({ctx, pk});
+        if (it == g_pk_handles.end()) return pk_fail(ctx, ZK_ERR_ARG, "%s: unknown key %llu", fn, (unsigned long long)pk);
+        h = it->second;
+        h->in_use++;
+    }
+    struct Done { zk_ctx* ctx; PkHandle* h; ~Done() { std::lock_guard<std::mutex> lk(g_pk_mu); if (--h->in_use == 0 && h->released) pk_drop(ctx, h); } } done{ctx, h};
+    return zk_plonk_create_proof_multi(ctx, &h->desc, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+}
+extern "C" int zk_plonk_prove(zk_ctx* ctx, uint64_t pk, const void* const* advice, int advice_on_device, const void* const* instances, const uint32_t* instance_lens,
+                              zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+    return prove_with_key("zk_plonk_prove", ctx, pk, 1, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
+                                    const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+    return prove_with_key("zk_plonk_prove_multi", ctx, pk, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+} ZK_ABI_CATCH(ctx)
+
+// zk_ctx_destroy (capi.hip): the keys this context still holds go with it (before its programs are released)
+void zk_internal_plonk_ctx_destroyed(zk_ctx* ctx) {
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    for (auto it = g_pk_handles.begin(); it != g_pk_handles.end();) {
+        if (it->first.first == ctx) { if (it->second->in_use) it->second->released = true; else pk_drop(ctx, it->second); it = g_pk_handles.erase(it); }
+        else ++it;
+    }
+}
