@@ -1,6 +1,7 @@
 // TEST-ONLY: runs the product's __host__ __device__ field / curve routines on the CPU so the
 // limb logic can be checked against the oracle without a GPU (tests/test_host_logic.py).
 // It is not a CPU fallback: the product library never links this file.
+#include <cstring>
 #include "../../zk-dcap-verifier_amd/csrc/ec.cuh"
 using namespace zk;
 template <class F29>
@@ -103,5 +104,33 @@ void hh_xyzz29_sum(const Affine* pts, const uint8_t* neg, size_t n, XYZZ* out, u
     }
     *out = xyzz29_leave(acc);
     *n_rare = rare;
+}
+// the one-limb filter of xyzz29_madd_fast.  One chain from `start` through the fast step itself, adding steps[i % n_steps] (points whose x differs from the
+// accumulator's) `len` times.  Before step i the accumulator is the point prefix[i] (the caller's, from the oracle): the fast step is offered (prefix[i].x, +y) and
+// (prefix[i].x, -y) — the same x, a doubling and a cancellation — and must refuse both and leave the accumulator as it was.  prefix == null: no probes.
+// counts[0] = collisions the filter let through, [1] = refusals that touched the accumulator, [2] = false alarms (refusals on the chain's own distinct-x additions, which
+// then take the complete step), [3] = steps after which the chain, left to canonical coordinates, differs from the same chain through xyzz_madd (check != 0).
+void hh_xyzz29_filter_probe(const Affine* start, const Affine* steps, size_t n_steps, const Affine* prefix, size_t len, int check, uint64_t* counts, XYZZ* out) {
+    XYZZ29 acc = xyzz29_identity();
+    xyzz29_madd(acc, start->x, start->y);
+    XYZZ ref = xyzz_from_affine(*start);
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    for (size_t i = 0; i < len; i++) {
+        if (prefix) {
+            for (int sign = 0; sign < 2; sign++) {
+                XYZZ29 t = acc;
+                if (xyzz29_madd_fast(t, prefix[i].x, sign ? Fq::neg(prefix[i].y) : prefix[i].y)) counts[0]++;
+                else if (memcmp(&t.x, &acc.x, 4 * sizeof(u261)) != 0 || t.ident != acc.ident) counts[1]++;
+            }
+        }
+        const Affine& s = steps[i % n_steps];
+        if (!xyzz29_madd_fast(acc, s.x, s.y)) { counts[2]++; xyzz29_madd(acc, s.x, s.y); }
+        if (check) {
+            xyzz_madd(ref, s.x, s.y);
+            const XYZZ l = xyzz29_leave(acc);
+            if (memcmp(&l, &ref, sizeof(XYZZ)) != 0) counts[3]++;
+        }
+    }
+    *out = xyzz29_leave(acc);
 }
 }

@@ -273,9 +273,9 @@ def check_fixed_base(be, orc, pyref, n, seed=61):
     be.g1_fixed_base_mul(ds, n, dout)
     got = dout.download((n, 8))
     g = orc.g1_generator()
-    for i in list(range(min(n, 6))) + [n - 1]:
-        want = orc.g1_to_affine(orc.g1_mul(g, sc[i]))[0]
-        assert (got[i] == want).all(), i
+    want = orc.g1_to_affine(np.stack([orc.g1_mul(g, s) for s in sc]))   # every output: one thread per scalar, each could be wrong on its own
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, bad[:8]
     ds.free()
     dout.free()
 

@@ -184,6 +184,48 @@ def test_lazy_mixed_addition_chain_equals_the_canonical_one(hh, orc, pyref):
     assert xyzz_to_affine(orc, p, o2) is None
 
 
+def _filter_chain(hh, orc, pyref, rnd, length, probes=True):
+    """one chain of hh_xyzz29_filter_probe: start = [a] G, the steps alternate [d] G and [e] G, so the accumulator before step 2m is [a + m (d + e)] G and before step
+    2m + 1 it is [a + d + m (d + e)] G — two arithmetic progressions of the oracle.  Returns the four counts and whether the end point is the oracle's."""
+    R = pyref.R
+    a, d, e = (rnd.randrange(1, R) for _ in range(3))
+    G = orc.g1_generator()
+    aff = lambda k: orc.g1_to_affine(orc.g1_mul(G, orc.fr_from_ints([k % R])[0]))[0]
+    start, steps = aff(a), np.ascontiguousarray(np.stack([aff(d), aff(e)]))
+    half = (length + 1) // 2
+    prefix = np.empty((2 * half, 8), dtype=np.uint64)
+    prefix[0::2] = orc.gen_bases_arith(a, (d + e) % R, half)
+    prefix[1::2] = orc.gen_bases_arith((a + d) % R, (d + e) % R, half)
+    assert (prefix[0] == start).all()
+    # the precondition, on the inputs: no step shares its x with the accumulator it meets (then every refusal of a step is a false alarm)
+    assert not (prefix[:length, :4] == steps[np.arange(length) % 2, :4]).all(axis=1).any()
+    counts, out = np.zeros(4, dtype=np.uint64), np.zeros(16, dtype=np.uint64)
+    hh.hh_xyzz29_filter_probe(P(start), P(steps), C.c_size_t(2), P(np.ascontiguousarray(prefix)) if probes else None, C.c_size_t(length), C.c_int(1), P(counts), P(out))
+    end = (a + (length // 2) * (d + e) + (d if length % 2 else 0)) % R
+    return [int(v) for v in counts], xyzz_to_affine(orc, pyref, out) == orc.g1_affine_to_ints(aff(end))[0]
+
+
+def test_fast_chain_filter_refuses_every_same_x_addition(hh, orc, pyref):
+    """xyzz29_madd_fast must return false — accumulator untouched — whenever the point shares its x with the accumulator (P = U2 - X1 + 8p is then j p for some j in 2 .. 9
+    by the bounds of ec.cuh; the filter looks at one limb of it).  600 seeded chains of 1 .. 128 steps (the longest sub-bucket) through the fast step itself, so the
+    accumulator's limbs sit wherever a real chain leaves them — a freshly entered point (ZZ = 1, X1 below p: j = 8, 9) up to X1 near its bound (small j); before EVERY
+    step the accumulator's own point is offered with +y (a doubling) and -y (a cancellation): about 77000 collisions, not one may pass.  On the chain's own additions (x
+    differs, asserted on the inputs) the result after every step equals the canonical xyzz_madd chain bit for bit, whether or not the filter raised a false alarm (ec.cuh
+    expects 2^-25 per addition: 11 residues of 2^29; the observed count is printed — at this size it is almost surely 0)."""
+    rnd = random.Random(29)
+    totals, steps = [0, 0, 0, 0], 0
+    for i in range(600):
+        length = 1 + (i * 37) % 128 if i >= 8 else (1, 2, 3, 127, 128, 64, 5, 96)[i]
+        counts, end_ok = _filter_chain(hh, orc, pyref, rnd, length)
+        assert end_ok
+        totals = [t + c for t, c in zip(totals, counts)]
+        steps += length
+    print("xyzz29_madd_fast: %d same-x probes, %d passed the filter; %d distinct-x additions, %d false alarms" % (2 * steps, totals[0], steps, totals[2]))
+    assert totals[0] == 0, "same-x additions went through the incomplete formulas"
+    assert totals[1] == 0, "a refused step changed the accumulator"
+    assert totals[3] == 0, "the 29-bit chain differs from the canonical one"
+
+
 def test_chained_copy_rows_equals_scalar_copy_and_is_a_bijection():
     """Assembly.copy_rows must only take its vectorised path for cells that are their own (singleton) cycle: `sizes` is kept for cycle
     representatives only, so after copy_rows(A, B) the B cells still read size 1 — a chained copy_rows(B, C) has to fall back to copy()."""
