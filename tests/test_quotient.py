@@ -107,7 +107,8 @@ def test_emulated_quotient_vs_oracle(emu, orc, pyref, seed, shape):
 @pytest.mark.parametrize("seed", [1, 2, 3, 5, 8])
 def test_emulated_quotient_dense_random_programs(emu, orc, pyref, seed):
     """60 random calculations per gate graph: values with several readers (a product that is folded AND read elsewhere must not be fused away), gate
-    polynomials that read PreviousValue themselves (the custom-gate Horner may then not run in the accumulator), Horner chains shared between lookups"""
+    polynomials that read PreviousValue themselves (the custom-gate Horner may then not run in the accumulator), Horner chains shared between lookups.  Several readers, not
+    long lives: each of these programs compiles to four slots (tests/test_structured_programs.py pins that, and runs the programs that need more)"""
     prog = qc.build_program(orc, pyref, seed=seed, gate_ops=60, k=4, cs_degree=5, n_fixed=4, n_advice=6, n_instance=1, n_challenges=1, n_perm=7, n_lookups=3)
     qc.run_case(emu, orc, pyref, pc, prog, seed=seed)
 
@@ -300,7 +301,9 @@ DENSE = dict(k=4, cs_degree=5, n_fixed=4, n_advice=6, n_instance=1, n_challenges
 
 
 def test_emulated_quotient_dense_program(emu, orc, pyref):
-    """60 gate operations over 6 advice columns, 7 permutation columns, 3 lookups: many live intermediates (LDS slots beyond the register slot)"""
+    """60 gate operations over 6 advice columns, 7 permutation columns, 3 lookups.  The compiled program keeps FOUR values live (the register slot and three LDS slots, 96
+    bytes per thread): build_program takes an operand from the earlier values with probability 1/2, so nearly every intermediate has one reader and dies at once.
+    Programs with many live intermediates — the other launch shapes of the interpreter — are in tests/test_structured_programs.py"""
     qc.run_case(emu, orc, pyref, pc, qc.build_program(orc, pyref, seed=5, gate_ops=60, **DENSE), seed=5)
 
 
