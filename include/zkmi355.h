@@ -52,9 +52,9 @@ typedef struct zk_ctx zk_ctx;
  * call instead of handing the library bytes past the end of its object.  Fields are only ever APPENDED, and each append bumps ZK_ABI_VERSION; a binding
  * asserts at start-up that zk_abi_version() is the ZK_ABI_VERSION it was written against and that zk_abi_struct_size(name) equals its own size of every
  * struct it declares (shim/halo2_proofs_mi355x/src/mi355x.rs does; tests/test_shim_abi.py diffs the declarations field by field). */
-#define ZK_ABI_VERSION 5u
+#define ZK_ABI_VERSION 6u
 uint32_t zk_abi_version(void);
-/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure") in this build of the library; 0 for an
+/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure", "zk_plonk_phases") in this build of the library; 0 for an
  * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify). */
 uint32_t zk_abi_struct_size(const char* struct_name);
 #define ZK_STRUCT_INIT(s) do { memset(&(s), 0, sizeof(s)); (s).struct_size = (uint32_t)sizeof(s); } while (0)   /* needs <string.h> */
@@ -333,7 +333,8 @@ int zk_evaluate_h(zk_ctx* ctx, uint64_t pk, const void* const* advice_polys, con
 
 /* ---- the whole per-proof path: replaces plonk::create_proof + ProverSHPLONK ------------------------------------- *
  * halo2_proofs src/plonk/prover.rs create_proof::<KZGCommitmentScheme<Bn256>, ProverSHPLONK, Challenge255, _, Blake2bWrite, _> as the reference calls it
- * (circuits/src/sgx_dcap_verifier.rs:814-822), one or several circuit instances (zk_plonk_create_proof_multi), no user challenges: every O(n) step runs through the entry points above in the
+ * (circuits/src/sgx_dcap_verifier.rs:814-822), one or several circuit instances (zk_plonk_create_proof_multi); multi-phase advice and user challenges go through
+ * zk_plonk_pk_build_phased / zk_plonk_prove_phased below (the descriptor-level calls here are single-phase): every O(n) step runs through the entry points above in the
  * order of INTEGRATION.md's phase table, columns stay in HBM from the advice commitment to the last SHPLONK commitment, Fiat-Shamir hashing (Blake2b,
  * Challenge255), point encoding (y parity in bit 255) and the rotation-set bookkeeping run on the host inside this call.  This is the native (C++) form of
  * the phase-batched prover; zk-dcap-verifier_amd/plonk/prover.py is its Python twin and both emit the same bytes for the same inputs and draws.
@@ -402,7 +403,8 @@ typedef struct zk_plonk_pk_desc {
  * so a proof consumes exactly the draws the CPU create_proof would and leaves the caller's rng in the same state (all draws are complete when the call returns ZK_OK).
  * Stack B's prover (halo2-axiom 0.4.2) is NOT claimed draw for draw: that fork commits with Blind::default() and is believed not to draw the Blinds ([3P-MEM], source
  * absent here), so under transcripts 1 / 2 the proofs verify and are deterministic in the rng stream, but byte parity with the axiom CPU prover is out of scope until its
- * schedule is pinned by shim/p256_k18_driver's dump.  Multi-phase advice and the Challenge API are not modelled either (zk_plonk_pk_build's caller must not pass such circuits). */
+ * schedule is pinned by shim/p256_k18_driver's dump.  Multi-phase advice and the Challenge API: draws follow halo2 phase by phase (zk_plonk_prove_phased below lists the order); zk_plonk_pk_build itself takes single-phase
+ * circuits only — a circuit with a later phase or a challenge is built with zk_plonk_pk_build_phased. */
 typedef void (*zk_rng_fn)(void* user, size_t n, void* out_fr);
 /* advice: n_advice columns of 2^k x 32 B (HOST, or DEVICE when advice_on_device — then consumed: their last rows take the blinding values, and they hold coefficient
  * forms or blinded values afterwards, whichever route the proof took); instances: HOST,
@@ -461,6 +463,47 @@ int zk_plonk_create_proof_multi(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_
                                 void* proof_out, size_t proof_cap, size_t* proof_len);
 int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
                          const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len);
+/* ---- multi-phase advice and halo2's Challenge API ([3P-MEM] PSE halo2_proofs v2023_01_20, src/plonk/{circuit,prover,verifier}.rs; the crate is not in this tree) ---- *
+ * advice_phase[c] in {0, 1, 2} is the phase of advice column c (ConstraintSystem::advice_column_phase), challenge_phase[i] the phase after which challenge i is
+ * squeezed (challenge_phase).  The phases in use are 0 ..= max(advice_phase); a column in phase p > 0 needs a column in phase p - 1; a challenge may become usable after
+ * any phase in use, the last one included.  The proof, in halo2's order: vk, instances; then for phase = 0, 1, ..: for circuit 0 .. m-1 the columns of that phase in
+ * ascending index — draws: their n - usable_rows blinding rows column by column, then one Blind per column — committed as one batch and written to the transcript;
+ * after the last circuit one squeeze per challenge of that phase in ascending index; then theta and everything else as zk_plonk_create_proof_multi.  Advice
+ * evaluations, the query list and SHPLONK follow the query log, not the phases.  With every column in phase 0 and no challenge this is zk_plonk_prove_multi, draw for
+ * draw and byte for byte.
+ * zk_plonk_pk_build_phased: zk_plonk_pk_build for such a circuit; the key keeps the two lists (zk_plonk_pk_share / _release / _descriptor work on it as on any key;
+ * the descriptor-level zk_plonk_create_proof* know no phases and refuse nothing: prove a phased key with zk_plonk_prove_phased).  ZK_ERR_ARG: a phase above 2, a gap
+ * (a column in phase p, none in p - 1), a challenge after a phase not in use, n_advice / n_challenges that disagree with host->n_advice or with the evaluator / lookup
+ * blobs' headers, host->shard_world > 1 (one proof over several GPUs stays single-phase).  ZK_ERR_LIMIT: more than ZK_MAX_CHALLENGES challenges (the quotient
+ * interpreter's constant bank is sized for no more).
+ * zk_phase_fn: called for phase = 1, 2, .. once the challenges of phase - 1 exist, on the thread that called zk_plonk_prove_phased, with no library lock held.
+ * `challenges`: HOST, n_challenges x 32 B Montgomery, entries not yet squeezed are zero.  `advice`: the caller's own n_circuits x n_advice pointer array (the one
+ * handed to zk_plonk_prove_phased): the callback stores the pointers of every column of `phase`, for all circuits — host or device as advice_on_device says — and
+ * the data must be complete when it returns.  A non-zero return or a pointer left NULL ends the proof with ZK_ERR_ARG, zk_last_error names the phase, the context
+ * stays usable.  While the callback runs, the library's helper context may still be transforming the columns of earlier phases (tunable "prover_side_lane").
+ * (Declared as a function type and a pointer to it: the same type as `int (*)(void*, uint32_t, const void*, uint32_t, const void**)`.) */
+#define ZK_MAX_CHALLENGES 256u
+typedef struct zk_plonk_phases zk_plonk_phases;
+struct zk_plonk_phases {
+    uint32_t struct_size;                       /* sizeof(zk_plonk_phases) of the caller (ABI versioning) */
+    uint32_t n_advice;
+    const uint8_t* advice_phase;                /* n_advice entries */
+    uint32_t n_challenges;
+    const uint8_t* challenge_phase;             /* n_challenges entries */
+};
+typedef int ZK_PHASE_CALLBACK(void* user, uint32_t phase, const void* challenges, uint32_t n_challenges, const void** advice);
+typedef ZK_PHASE_CALLBACK* zk_phase_fn;
+int zk_plonk_pk_build_phased(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk);
+/* advice: n_circuits x n_advice pointers, circuit-major, WRITABLE by the callback; entries of later-phase columns are ignored at entry (the library clears them before
+ * the first callback).  next_phase = NULL on a key with later phases: ZK_ERR_ARG.  On a key without later phases or challenges: byte for byte zk_plonk_prove_multi.
+ * With advice_on_device every column is consumed as zk_plonk_create_proof describes, column by column. */
+int zk_plonk_prove_phased(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void** advice, int advice_on_device, const void* const* instances,
+                          const uint32_t* instance_lens, zk_phase_fn next_phase, void* next_phase_user, zk_rng_fn rng, void* rng_user,
+                          void* proof_out, size_t proof_cap, size_t* proof_len);
+/* what the calling thread's last proof (any zk_plonk_create_proof* / zk_plonk_prove*) squeezed, canonical 32-byte little endian: the user challenges in index order,
+ * then theta, beta, gamma, y, x and SHPLONK's y, v, u — for a caller that replays the transcript and compares.  *n = their number (n_challenges + 8; fewer after a
+ * proof that failed early); ZK_ERR_LIMIT when cap (in bytes) is too small, *n still set. */
+int zk_plonk_last_challenges(void* out, size_t cap, size_t* n);
 /* wall milliseconds of the nine phases (instances, advice, lookups, grand products, random poly, h numerator, h commit, evaluations, SHPLONK) of the
  * calling thread's last zk_plonk_create_proof / zk_plonk_create_proof_multi (a phase of an m-circuit proof covers all m circuits) */
 int zk_plonk_last_phase_ms(double out[9]);
@@ -469,7 +512,8 @@ int zk_plonk_trim(zk_ctx* ctx);
 
 /* ---- MockProver: halo2_proofs::dev::MockProver::verify on the device ------------------------------------------------------------------------------------ *
  * The witness check the reference runs before it proves (MockProver::run(k, &circuit, vec![]).assert_satisfied(), circuits/src/sgx_dcap_verifier.rs:790-794), for
- * single-phase circuits without challenges, with the semantics of zk-dcap-verifier_amd/plonk/dev.py's MockProver.verify (u = 2^k - blinding_factors - 1):
+ * circuits of any number of phases (zk_mock_prover_verify: single-phase circuits without challenges; zk_mock_prover_verify_phased: the caller passes the challenge
+ * values), with the semantics of zk-dcap-verifier_amd/plonk/dev.py's MockProver.verify (u = 2^k - blinding_factors - 1):
  *   gates    every polynomial of cs.gates on rows 0 .. u-1, rotations taken mod 2^k;
  *   lookups  for every lookup and every input row r < u: the input tuple occurs among the table tuples of rows < u;
  *   copies   for every permutation column j and every row of 2^k: the value of (j, row) equals the value of map(j, row), both fully reduced.
@@ -478,7 +522,7 @@ int zk_plonk_trim(zk_ctx* ctx);
  * the library draws per call (r over the gate polynomials, theta over a lookup tuple's expressions): a failing row goes unseen with probability at most E / |Fr|
  * (E gate polynomials), a missing tuple of m expressions at most (m - 1) / |Fr|; which polynomial of a failing row failed is decided exactly.
  * ZK_ERR_ARG: a wrong struct_size, NULL columns, a blob for another k or other column counts, a non-canonical instance, a mapping entry out of range;
- * ZK_ERR_PROGRAM: a blob that declares challenges (n_challenges > 0: the native prover does not model them either).
+ * ZK_ERR_PROGRAM: a blob that declares challenges (n_challenges > 0) handed to zk_mock_prover_verify: the values come through zk_mock_prover_verify_phased.
  * zk_mock_failure is an output record and carries no struct_size; both structs are sized by zk_abi_struct_size. */
 typedef struct zk_mock_desc zk_mock_desc;
 typedef struct zk_mock_failure zk_mock_failure;
@@ -504,6 +548,10 @@ struct zk_mock_failure {
     uint32_t other_column, other_row;           /* copy only: the mapped cell (perm_columns index, row) */
 };
 int zk_mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* desc, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written);
+/* the same checks with the caller's challenge values fed to the gate and lookup programs (HOST, n_challenges x 32 B Montgomery: what halo2's MockProver derives):
+ * every blob must declare exactly n_challenges challenges (ZK_ERR_ARG otherwise); n_challenges = 0 takes what zk_mock_prover_verify takes. */
+int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const void* challenges, uint32_t n_challenges, zk_mock_failure* out, size_t cap,
+                                 uint64_t counts[3], size_t* n_written);
 
 /* library / build identification */
 const char* zk_version(void);

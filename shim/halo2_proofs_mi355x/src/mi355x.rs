@@ -17,7 +17,7 @@ pub struct ZkCtx {
 }
 
 /// ZK_ABI_VERSION of the include/zkmi355.h this file was written against
-pub const ZK_ABI_VERSION: u32 = 5;
+pub const ZK_ABI_VERSION: u32 = 6;
 
 /// field-for-field `zk_quotient_args`
 #[repr(C)]
@@ -49,6 +49,8 @@ pub struct ZkQuotientArgs {
 pub struct ZkPlonkPkDesc { _opaque: [u8; 0] }
 /// zk_rng_fn: the caller's `Fr::random` (create_proof_native.rs: `draw`)
 pub type ZkRngFn = extern "C" fn(user: *mut c_void, n: usize, out_fr: *mut c_void);
+/// zk_phase_fn: the caller's synthesis of advice phase 1, 2 (create_proof_native.rs: `next_phase`).  The header declares it as a function type and a pointer to it.
+pub type ZkPhaseFn = unsafe extern "C" fn(user: *mut c_void, phase: u32, challenges: *const c_void, n_challenges: u32, advice: *mut *const c_void) -> c_int;
 
 extern "C" {
     /// one proof over several circuits (halo2's `&[c0, c1, ..]`): advice = n_circuits x n_advice, instances / instance_lens = n_circuits x n_instance, circuit-major
@@ -59,6 +61,12 @@ extern "C" {
                           instance_lens: *const u32, rng: ZkRngFn, rng_user: *mut c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
     pub fn zk_plonk_prove_multi(ctx: *mut ZkCtx, pk: u64, n_circuits: u32, advice: *const *const c_void, advice_on_device: c_int, instances: *const *const c_void,
                                 instance_lens: *const u32, rng: ZkRngFn, rng_user: *mut c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    /// advice in phases with user challenges between them: `advice` is writable (the callback stores the later phases' columns); a key without later phases: zk_plonk_prove_multi
+    pub fn zk_plonk_prove_phased(ctx: *mut ZkCtx, pk: u64, n_circuits: u32, advice: *mut *const c_void, advice_on_device: c_int, instances: *const *const c_void,
+                                 instance_lens: *const u32, next_phase: Option<ZkPhaseFn>, next_phase_user: *mut c_void, rng: ZkRngFn, rng_user: *mut c_void,
+                                 proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
+    /// what the calling thread's last proof squeezed, canonical little endian: user challenges, theta, beta, gamma, y, x, SHPLONK's y, v, u
+    pub fn zk_plonk_last_challenges(out: *mut c_void, cap: usize, n: *mut usize) -> c_int;
     /// halo2's fold across circuits: out <- out * y^E + numerator (coset = u32::MAX: the whole extended domain; part 0 whole, 1 high, 2 low)
     pub fn zk_quotient_run_acc_dev(ctx: *mut ZkCtx, prog: u64, args: *const ZkQuotientArgs, coset: u32, part: u32) -> c_int;
 }
@@ -123,6 +131,7 @@ pub fn gpu() -> Option<&'static Gpu> {
         assert_eq!(unsafe { zk_abi_version() }, ZK_ABI_VERSION, "libzkmi355.so ABI version differs from the binding's");
         assert_eq!(unsafe { zk_abi_struct_size(b"zk_quotient_args\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<ZkQuotientArgs>());
         assert_eq!(unsafe { zk_abi_struct_size(b"zk_plonk_pk_host\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::pk_desc::ZkPlonkPkHost>());
+        assert_eq!(unsafe { zk_abi_struct_size(b"zk_plonk_phases\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::pk_desc::ZkPlonkPhases>());
         let dev = std::env::var("HALO2_MI355X_DEVICE").ok().and_then(|s| s.parse().ok()).unwrap_or(0);
         let mut ctx = std::ptr::null_mut();
         if unsafe { zk_ctx_create(dev, &mut ctx) } != 0 {

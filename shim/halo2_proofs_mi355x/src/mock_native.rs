@@ -1,8 +1,8 @@
 //! MockProver on the GPU: the declarations of `zk_mock_prover_verify` (include/zkmi355.h; csrc/mockprover.hip) and the translation of its records into
 //! halo2's `VerifyFailure`s.  `mod mock_native;` next to `mod mi355x;`, hooked into dev.rs by dev_native.patch.  Uncompiled in the build image (no rustc there).
 //!
-//! Guards (any failing -> None -> the CPU body of MockProver::verify runs as before): HALO2_MI355X != 0 and a gfx950 context exists (mi355x::gpu()); one advice
-//! phase and no challenges; n >= 2^12 (mi355x::MIN_LEN).  Gate, lookup and permutation failures then come from the device; CellNotAssigned and the other checks of
+//! Guards (any failing -> None -> the CPU body of MockProver::verify runs as before): HALO2_MI355X != 0 and a gfx950 context exists (mi355x::gpu());
+//! n >= 2^12 (mi355x::MIN_LEN).  A circuit with user challenges passes the values halo2's MockProver derived (`MockInput::challenges`, zk_mock_prover_verify_phased).  Gate, lookup and permutation failures then come from the device; CellNotAssigned and the other checks of
 //! the regions' metadata stay on the CPU body, which the patch runs with those three loops skipped.
 use std::ffi::c_void;
 use std::os::raw::c_int;
@@ -50,6 +50,8 @@ pub struct ZkMockFailure {
 
 extern "C" {
     pub fn zk_mock_prover_verify(ctx: *mut ZkCtx, desc: *const ZkMockDesc, out: *mut ZkMockFailure, cap: usize, counts: *mut u64, n_written: *mut usize) -> c_int;
+    pub fn zk_mock_prover_verify_phased(ctx: *mut ZkCtx, desc: *const ZkMockDesc, challenges: *const c_void, n_challenges: u32, out: *mut ZkMockFailure, cap: usize,
+                                        counts: *mut u64, n_written: *mut usize) -> c_int;
 }
 
 /// What MockProver::verify owns, flattened for the call: the Evaluator / lookup blobs of the circuit's ConstraintSystem (evaluation_zkq1.rs), the columns as
@@ -66,6 +68,8 @@ pub struct MockInput<'a> {
     pub instances: &'a [Vec<[u8; 32]>],
     pub map_column: &'a [u32],
     pub map_row: &'a [u32],
+    /// MockProver's `challenges: Vec<F>` (Fr is its Montgomery limbs in memory); empty for a circuit without the Challenge API
+    pub challenges: &'a [halo2curves::bn256::Fr],
 }
 
 /// All failures in MockProver's order (gates by (row, polynomial), lookups by (lookup, row), copies by (column, row)) and the exact counts, or None when a
@@ -107,15 +111,16 @@ pub fn verify(inp: &MockInput) -> Option<(Vec<ZkMockFailure>, [u64; 3])> {
     };
     let mut counts = [0u64; 3];
     let mut written = 0usize;
+    let (ch, n_ch) = (inp.challenges.as_ptr() as *const c_void, inp.challenges.len() as u32);
     // first call: the counts (cap 0); second: every record
-    if unsafe { zk_mock_prover_verify(g.ctx, &d, std::ptr::null_mut(), 0, counts.as_mut_ptr(), &mut written) } != 0 {
-        g.complain("zk_mock_prover_verify");
+    if unsafe { zk_mock_prover_verify_phased(g.ctx, &d, ch, n_ch, std::ptr::null_mut(), 0, counts.as_mut_ptr(), &mut written) } != 0 {
+        g.complain("zk_mock_prover_verify_phased");
         return None;
     }
     let total = (counts[0] + counts[1] + counts[2]) as usize;
     let mut out = vec![ZkMockFailure::default(); total];
-    if total > 0 && unsafe { zk_mock_prover_verify(g.ctx, &d, out.as_mut_ptr(), total, counts.as_mut_ptr(), &mut written) } != 0 {
-        g.complain("zk_mock_prover_verify");
+    if total > 0 && unsafe { zk_mock_prover_verify_phased(g.ctx, &d, ch, n_ch, out.as_mut_ptr(), total, counts.as_mut_ptr(), &mut written) } != 0 {
+        g.complain("zk_mock_prover_verify_phased");
         return None;
     }
     out.truncate(written);

@@ -50,8 +50,20 @@ pub struct ZkPlonkPkHost {
     pub allgather_user: *mut c_void,
 }
 
+/// field-for-field `zk_plonk_phases`: cs.advice_column_phase and cs.challenge_phase as bytes
+#[repr(C)]
+#[derive(Debug)]
+pub struct ZkPlonkPhases {
+    pub struct_size: u32,
+    pub n_advice: u32,
+    pub advice_phase: *const u8,
+    pub n_challenges: u32,
+    pub challenge_phase: *const u8,
+}
+
 extern "C" {
     fn zk_plonk_pk_build(ctx: *mut ZkCtx, host: *const ZkPlonkPkHost, srs_g: u64, srs_g_lagrange: u64, pk: *mut u64) -> c_int;
+    fn zk_plonk_pk_build_phased(ctx: *mut ZkCtx, host: *const ZkPlonkPkHost, phases: *const ZkPlonkPhases, srs_g: u64, srs_g_lagrange: u64, pk: *mut u64) -> c_int;
     fn zk_plonk_pk_release(ctx: *mut ZkCtx, pk: u64) -> c_int;
 }
 
@@ -66,8 +78,9 @@ fn column_type_code(any: &Any) -> u32 {
     }
 }
 
-/// The key object for (params, pk) on the process's GPU context, built on first use.  None = this ProvingKey cannot take the one-call path (user challenges /
-/// multi-phase advice, or a library error — reported through Gpu::complain): the caller runs the CPU body.
+/// The key object for (params, pk) on the process's GPU context, built on first use: zk_plonk_pk_build for a single-phase circuit, zk_plonk_pk_build_phased (the key
+/// keeps cs.advice_column_phase / cs.challenge_phase) for one with later advice phases or user challenges.  None = a library error — reported through
+/// Gpu::complain, e.g. more challenges than ZK_MAX_CHALLENGES: the caller runs the CPU body.
 pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Affine>) -> Option<u64> {
     let id = (pk as *const _ as usize, params.g.as_ptr() as usize);
     let mut guard = KEYS.lock().unwrap();
@@ -76,10 +89,10 @@ pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Aff
         return Some(*h);
     }
     let cs = &pk.vk.cs;
-    // the native prover implements halo2's single-phase flow: one advice phase, no Challenge API (the reference's circuits use neither)
-    if cs.num_challenges != 0 || cs.advice_column_phase.iter().any(|p| p.0 != 0) {
-        return None;
-    }
+    // [3P-MEM] sealed::Phase(u8): advice_column_phase[c] / challenge_phase[i] in 0 ..= 2
+    let advice_phase: Vec<u8> = cs.advice_column_phase.iter().map(|p| p.0).collect();
+    let challenge_phase: Vec<u8> = cs.challenge_phase.iter().map(|p| p.0).collect();
+    let phased = cs.num_challenges != 0 || advice_phase.iter().any(|p| *p != 0);
     let k = params.k;
     let n = 1usize << k;
     let srs_g = g.table_for(&params.g[..n])?;               // pub(crate) in mi355x.rs; also enables the run-length twin (zk_bases_enable_runs)
@@ -126,8 +139,14 @@ pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Aff
         shard_world: 0, shard_rank: 0, allgather: None, allgather_user: std::ptr::null_mut(),
     };
     let mut handle = 0u64;
-    if unsafe { zk_plonk_pk_build(g.ctx, &host, srs_g, srs_gl, &mut handle) } != 0 {
-        g.complain("zk_plonk_pk_build");
+    let phases = ZkPlonkPhases {
+        struct_size: std::mem::size_of::<ZkPlonkPhases>() as u32,
+        n_advice: advice_phase.len() as u32, advice_phase: advice_phase.as_ptr(),
+        n_challenges: challenge_phase.len() as u32, challenge_phase: challenge_phase.as_ptr(),
+    };
+    let rc = if phased { unsafe { zk_plonk_pk_build_phased(g.ctx, &host, &phases, srs_g, srs_gl, &mut handle) } } else { unsafe { zk_plonk_pk_build(g.ctx, &host, srs_g, srs_gl, &mut handle) } };
+    if rc != 0 {
+        g.complain(if phased { "zk_plonk_pk_build_phased" } else { "zk_plonk_pk_build" });
         return None;
     }
     map.insert(id, handle);

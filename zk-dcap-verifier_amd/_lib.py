@@ -26,7 +26,7 @@ class ZkError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 5          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
+ABI_VERSION = 6          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
 
 
 class QuotientArgs(C.Structure):
@@ -53,6 +53,14 @@ class MockDesc(C.Structure):
                 ("values_on_device", C.c_uint32)]
 
 
+class PlonkPhases(C.Structure):
+    """zk_plonk_phases (zk_plonk_pk_build_phased)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_advice", C.c_uint32), ("advice_phase", C.c_void_p), ("n_challenges", C.c_uint32), ("challenge_phase", C.c_void_p)]
+
+
+PHASE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))     # zk_phase_fn
+
+
 class MockFailure(C.Structure):
     """zk_mock_failure: kind 0 gate / 1 lookup / 2 copy"""
     _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("other_column", C.c_uint32), ("other_row", C.c_uint32)]
@@ -74,7 +82,7 @@ def _load(path: str):
         raise RuntimeError(f"{path}: ABI version {lib.zk_abi_version()}, this binding is written against {ABI_VERSION} (rebuild: __graft_entry__.build())")
     if lib.zk_abi_struct_size(b"zk_quotient_args") != C.sizeof(QuotientArgs):
         raise RuntimeError(f"{path}: sizeof(zk_quotient_args) = {lib.zk_abi_struct_size(b'zk_quotient_args')}, the binding's QuotientArgs has {C.sizeof(QuotientArgs)}")
-    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure)):
+    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure), (b"zk_plonk_phases", PlonkPhases)):
         if lib.zk_abi_struct_size(name) != C.sizeof(st):
             raise RuntimeError(f"{path}: sizeof({name.decode()}) = {lib.zk_abi_struct_size(name)}, the binding's {st.__name__} has {C.sizeof(st)}")
     return lib
@@ -493,7 +501,7 @@ class Backend:
     # -- MockProver ------------------------------------------------------------------------------
     def mock_prover_verify(self, *, k: int, blinding_factors: int, n_fixed: int, n_advice: int, n_instance: int, perm_columns, evaluator_blob: bytes,
                            lookup_input_blobs, lookup_table_blobs, fixed, advice, instances, perm_map_column=None, perm_map_row=None, cap: int = 0,
-                           struct_size: int | None = None):
+                           struct_size: int | None = None, challenges=None):
         """zk_mock_prover_verify.  fixed / advice: (2^k, 4) uint64 Montgomery arrays (host) or device buffers (all of one kind; None = a NULL column);
         instances: canonical ints per instance column; perm_map_column / perm_map_row: (n_perm_columns, 2^k) integer arrays (Assembly.map_c / map_r).
         Returns ([(kind, index, row, other_column, other_row)] for the first `cap` failures, (gate, lookup, copy) counts)."""
@@ -541,7 +549,13 @@ class Backend:
         out = (MockFailure * max(1, cap))()
         counts = (C.c_uint64 * 3)()
         written = C.c_size_t()
-        self._ck(self.lib.zk_mock_prover_verify(self.ctx, C.byref(d), out, C.c_size_t(cap), counts, C.byref(written)))
+        if challenges is None:
+            self._ck(self.lib.zk_mock_prover_verify(self.ctx, C.byref(d), out, C.c_size_t(cap), counts, C.byref(written)))
+        else:                                                            # zk_mock_prover_verify_phased: canonical ints -> Montgomery limbs
+            from .fields import fr_mont_array
+            ch = np.ascontiguousarray(fr_mont_array([int(c) for c in challenges]) if len(challenges) else np.zeros((1, 4), np.uint64))
+            self._ck(self.lib.zk_mock_prover_verify_phased(self.ctx, C.byref(d), ch.ctypes.data_as(C.c_void_p), C.c_uint32(len(challenges)), out, C.c_size_t(cap),
+                                                           counts, C.byref(written)))
         recs = [(f.kind, f.index, f.row, f.other_column, f.other_row) for f in out[: written.value]]
         return recs, (int(counts[0]), int(counts[1]), int(counts[2]))
 

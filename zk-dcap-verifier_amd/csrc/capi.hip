@@ -50,7 +50,8 @@ int quotient_program_opmix(zk_ctx* ctx, uint64_t prog, uint32_t part, uint32_t c
 struct QuotRowList;
 int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
                  const QuotRowList* rl = nullptr);
-int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written);
+int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written, const void* challenges = nullptr,
+                       uint32_t n_challenges = 0, bool phased = false);
 int quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low);
 int domain_coeff_to_coset_batch(zk_ctx* ctx, const void* const* coeffs, void* const* outs, size_t count, uint32_t k, uint32_t ek, uint32_t coset);
 int fr_interleave(zk_ctx* ctx, const void* const* h_cosets, size_t count, size_t n, void* d_out);
@@ -151,6 +152,7 @@ uint32_t zk_abi_struct_size(const char* name) ZK_ABI_TRY {
     if (!strcmp(name, "zk_plonk_pk_host")) return (uint32_t)sizeof(zk_plonk_pk_host);
     if (!strcmp(name, "zk_mock_desc")) return (uint32_t)sizeof(zk_mock_desc);
     if (!strcmp(name, "zk_mock_failure")) return (uint32_t)sizeof(zk_mock_failure);
+    if (!strcmp(name, "zk_plonk_phases")) return (uint32_t)sizeof(zk_plonk_phases);
     return 0;
 } ZK_ABI_CATCH_VALUE(nullptr, 0u)
 
@@ -534,6 +536,13 @@ int zk_quotient_program_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_prog, u
 // MockProver::verify on the device (csrc/mockprover.hip)
 int zk_mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* desc, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written) ZK_ABI_TRY {
     ENTER; return mock_prover_verify(ctx, desc, out, cap, counts, n_written);
+} ZK_ABI_CATCH(ctx)
+int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const void* challenges, uint32_t n_challenges, zk_mock_failure* out, size_t cap,
+                                 uint64_t counts[3], size_t* n_written) ZK_ABI_TRY {
+    ENTER;
+    if (n_challenges && !challenges) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify_phased: %u challenges and a null array", n_challenges);
+    if (n_challenges > ZK_MAX_CHALLENGES) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_verify_phased: %u challenges, the quotient interpreter's constant bank is sized for %u", n_challenges, ZK_MAX_CHALLENGES);
+    return mock_prover_verify(ctx, desc, out, cap, counts, n_written, challenges, n_challenges, true);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 0, 0, 0); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset) ZK_ABI_TRY {

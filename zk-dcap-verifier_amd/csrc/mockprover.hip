@@ -244,7 +244,9 @@ struct MpTimer {                                 // one pass under HIP events (z
 };
 }  // namespace
 
-int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written) {
+// challenges / n_challenges (zk_mock_prover_verify_phased, `phased`): the values of the circuit's user challenges, Montgomery, fed to every program as they are
+int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written, const void* challenges,
+                       uint32_t n_challenges, bool phased) {
     if (!d) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: null descriptor");
     if (d->struct_size != sizeof(zk_mock_desc))
         return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: zk_mock_desc.struct_size %u, expected %zu (ABI version %u)", d->struct_size, sizeof(zk_mock_desc), ZK_ABI_VERSION);
@@ -270,7 +272,8 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
         uint32_t w[7];
         memcpy(w, blob, sizeof w);
         if (w[0] != 0x31514B5Au) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_verify: %s blob %u: bad magic", what, i);
-        if (w[6]) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_verify: %s blob %u declares %u challenges (multi-phase circuits are not modelled)", what, i, w[6]);
+        if (w[6] && !phased) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_verify: %s blob %u declares %u challenges (their values go to zk_mock_prover_verify_phased)", what, i, w[6]);
+        if (w[6] != n_challenges) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify_phased: %s blob %u declares %u challenges, the caller passed %u", what, i, w[6], n_challenges);
         if (w[1] != k || (!evaluator && w[2] != k)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: %s blob %u is for k = %u / extended_k = %u, not k = %u", what, i, w[1], w[2], k);
         if (w[3] != F || w[4] != A || w[5] != I) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_verify: %s blob %u has %u / %u / %u fixed / advice / instance columns, the descriptor %u / %u / %u",
                                                                    what, i, w[3], w[4], w[5], F, A, I);
@@ -329,7 +332,7 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
     ZK_STRUCT_INIT(qa);
     qa.fixed = fx.data(); qa.advice = ad.data(); qa.instance = in.data();
     qa.l0 = qa.l_last = qa.l_active_row = zero_col;
-    qa.challenges = &one; qa.beta = &one; qa.gamma = &one; qa.theta = &theta; qa.y = &r;
+    qa.challenges = n_challenges ? challenges : (const void*)&one; qa.beta = &one; qa.gamma = &one; qa.theta = &theta; qa.y = &r;
     const uint32_t blk = 256;
 
     // ---- 4. copies (first: a mapping out of range is an argument error, found before the other passes run) ----------------------------------------------------

@@ -23,6 +23,8 @@ struct PkMem {
     std::vector<const void*> coset_fixed, coset_sigma, coset_l;      // a sharded key: [this rank's cosets][columns], n values each
     std::vector<uint32_t> perm_columns, advice_queries, fixed_queries, table_key;
     uint8_t transcript_repr[32];
+    bool phased = false;                                              // built by zk_plonk_pk_build_phased: the two lists below are the circuit's
+    std::vector<uint8_t> advice_phase, challenge_phase;               // ([3P-MEM] plonk/circuit.rs advice_column_phase, challenge_phase)
     int holders = 0;
 };
 struct PkHandle {
@@ -62,7 +64,42 @@ void pk_drop(zk_ctx* ctx, PkHandle* h) {                              // g_pk_mu
 }
 }  // namespace
 
-extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
+// The phase lists of a phased key against halo2's rules and against the blobs the key is built from (word 6 of a ZKQ1 header: n_challenges; word 4: n_advice)
+static int check_phases(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* ph) {
+    if (ph->struct_size != sizeof(zk_plonk_phases))
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: zk_plonk_phases.struct_size %u, expected %zu (ABI version %u)", ph->struct_size, sizeof(zk_plonk_phases), ZK_ABI_VERSION);
+    if (host->shard_world > 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: shard_world %u: one proof over several GPUs is single-phase", host->shard_world);
+    if (ph->n_challenges > ZK_MAX_CHALLENGES)
+        return pk_fail(ctx, ZK_ERR_LIMIT, "zk_plonk_pk_build_phased: %u challenges, the quotient interpreter's constant bank is sized for %u", ph->n_challenges, ZK_MAX_CHALLENGES);
+    if (ph->n_advice != host->n_advice) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: phases for %u advice columns, the key has %u", ph->n_advice, host->n_advice);
+    if ((ph->n_advice && !ph->advice_phase) || (ph->n_challenges && !ph->challenge_phase)) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: null phase list");
+    uint32_t count[3] = {0, 0, 0};
+    for (uint32_t i = 0; i < ph->n_advice; i++) {
+        if (ph->advice_phase[i] > 2) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: advice column %u in phase %u (0 .. 2)", i, ph->advice_phase[i]);
+        count[ph->advice_phase[i]]++;
+    }
+    for (uint32_t p = 1; p < 3; p++)
+        if (count[p] && !count[p - 1]) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: an advice column in phase %u and none in phase %u", p, p - 1);
+    const uint32_t last = count[2] ? 2 : count[1] ? 1 : 0;
+    for (uint32_t i = 0; i < ph->n_challenges; i++)
+        if (ph->challenge_phase[i] > last) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: challenge %u after phase %u, the last phase in use is %u", i, ph->challenge_phase[i], last);
+    auto header = [&](const void* blob, size_t len, const char* what, uint32_t i) -> int {
+        uint32_t w[7];
+        if (!blob || len < sizeof w) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: bad %s blob %u", what, i);
+        memcpy(w, blob, sizeof w);
+        if (w[4] != ph->n_advice || w[6] != ph->n_challenges)
+            return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build_phased: %s blob %u declares %u advice columns and %u challenges, the phase lists %u and %u", what, i, w[4], w[6], ph->n_advice, ph->n_challenges);
+        return ZK_OK;
+    };
+    PK(header(host->evaluator_zkq1, host->evaluator_zkq1_len, "evaluator", 0));
+    for (uint32_t l = 0; l < host->n_lookups; l++) {
+        PK(header(host->lookup_input_zkq1[l], host->lookup_input_zkq1_len[l], "lookup input", l));
+        PK(header(host->lookup_table_zkq1[l], host->lookup_table_zkq1_len[l], "lookup table", l));
+    }
+    return ZK_OK;
+}
+
+static int pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) {
     if (!ctx || !host || !pk) return ZK_ERR_ARG;
     if (host->struct_size != sizeof(zk_plonk_pk_host))
         return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build: zk_plonk_pk_host.struct_size %u, expected %zu (ABI version %u)", host->struct_size, sizeof(zk_plonk_pk_host), ZK_ABI_VERSION);
@@ -72,6 +109,7 @@ extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint
         (host->n_fixed_queries && !host->fixed_queries) ||
         (L && (!host->lookup_input_zkq1 || !host->lookup_input_zkq1_len || !host->lookup_table_zkq1 || !host->lookup_table_zkq1_len || !host->lookup_table_key)))
         return ZK_ERR_ARG;
+    if (phases) PK(check_phases(ctx, host, phases));
     const size_t n = (size_t)1 << k, col_bytes = n * 32;
     if ((size_t)host->blinding_factors + 2 >= n) return ZK_ERR_ARG;
     uint32_t ek = k;                                                  // EvaluationDomain::new(j, k): the smallest extended domain that holds a quotient of degree (j - 1) n
@@ -178,6 +216,11 @@ extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint
     h->in_prog.push_back(0); h->tab_prog.push_back(0);
     for (auto* v : {&m->fixed_values, &m->fixed_polys, &m->fixed_cosets, &m->sigma_values, &m->sigma_polys, &m->sigma_cosets, &m->coset_fixed, &m->coset_sigma, &m->coset_l}) v->push_back(nullptr);
     memcpy(m->transcript_repr, host->transcript_repr, 32);
+    if (phases) {
+        m->phased = true;
+        m->advice_phase.assign(phases->advice_phase, phases->advice_phase + phases->n_advice);
+        m->challenge_phase.assign(phases->challenge_phase, phases->challenge_phase + phases->n_challenges);
+    }
     zk_plonk_pk_desc shape;
     ZK_STRUCT_INIT(shape);
     shape.k = k; shape.extended_k = ek; shape.cs_degree = host->cs_degree; shape.blinding_factors = host->blinding_factors;
@@ -193,6 +236,16 @@ extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint
     }
     undo.h = nullptr;
     return ZK_OK;
+}
+
+extern "C" int zk_plonk_pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
+    return pk_build(ctx, host, nullptr, srs_g, srs_g_lagrange, pk);
+} ZK_ABI_CATCH(ctx)
+
+// zk_plonk_pk_build for a circuit with advice in several phases and user challenges: the same key, and the two lists kept with it
+extern "C" int zk_plonk_pk_build_phased(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
+    if (!ctx || !host || !phases || !pk) return ZK_ERR_ARG;
+    return pk_build(ctx, host, phases, srs_g, srs_g_lagrange, pk);
 } ZK_ABI_CATCH(ctx)
 
 extern "C" int zk_plonk_pk_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_pk, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) ZK_ABI_TRY {
@@ -242,7 +295,8 @@ extern "C" int zk_plonk_pk_descriptor(zk_ctx* ctx, uint64_t pk, const zk_plonk_p
 
 // zk_plonk_prove / zk_plonk_prove_multi: the handle (descriptor, programs, its share of the columns) stays alive for the whole proof whatever other threads release meanwhile
 static int prove_with_key(const char* fn, zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
-                          const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) {
+                          const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len,
+                          bool phased = false, const void** advice_out = nullptr, zk_phase_fn next_phase = nullptr, void* next_phase_user = nullptr) {
     if (!ctx) return ZK_ERR_ARG;
     PkHandle* h = nullptr;
     {
@@ -253,6 +307,12 @@ static int prove_with_key(const char* fn, zk_ctx* ctx, uint64_t pk, uint32_t n_c
         h->in_use++;
     }
     struct Done { zk_ctx* ctx; PkHandle* h; ~Done() { std::lock_guard<std::mutex> lk(g_pk_mu); if (--h->in_use == 0 && h->released) pk_drop(ctx, h); } } done{ctx, h};
+    if (phased && h->mem->phased) {                                   // (a key of zk_plonk_pk_build has no later phase and no challenge: zk_plonk_prove_multi, byte for byte)
+        PhaseSpec ph;
+        ph.advice_phase = h->mem->advice_phase.data(); ph.challenge_phase = h->mem->challenge_phase.data(); ph.n_challenges = (uint32_t)h->mem->challenge_phase.size();
+        ph.next_phase = next_phase; ph.next_phase_user = next_phase_user; ph.advice_out = advice_out;
+        return create_proof_phased(ctx, &h->desc, &ph, n_circuits, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+    }
     return zk_plonk_create_proof_multi(ctx, &h->desc, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
 }
 extern "C" int zk_plonk_prove(zk_ctx* ctx, uint64_t pk, const void* const* advice, int advice_on_device, const void* const* instances, const uint32_t* instance_lens,
@@ -263,6 +323,13 @@ extern "C" int zk_plonk_prove(zk_ctx* ctx, uint64_t pk, const void* const* advic
 extern "C" int zk_plonk_prove_multi(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void* const* advice, int advice_on_device, const void* const* instances,
                                     const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
     return prove_with_key("zk_plonk_prove_multi", ctx, pk, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_prove_phased(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const void** advice, int advice_on_device, const void* const* instances,
+                                     const uint32_t* instance_lens, zk_phase_fn next_phase, void* next_phase_user, zk_rng_fn rng, void* rng_user,
+                                     void* proof_out, size_t proof_cap, size_t* proof_len) ZK_ABI_TRY {
+    return prove_with_key("zk_plonk_prove_phased", ctx, pk, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len,
+                          true, advice, next_phase, next_phase_user);
 } ZK_ABI_CATCH(ctx)
 
 // zk_ctx_destroy (capi.hip): the keys this context still holds go with it (before its programs are released)

@@ -1,4 +1,4 @@
-// What the proving-key object (pk.hip) and the proof (prover.hip) share, and nothing else: the way both report an error, and the rule that gives every rank of a
+// What the proving-key object (pk.hip) and the proof (prover.hip) share, and nothing else: the way both report an error, the phase lists of a phased key, and the rule that gives every rank of a
 // sharded key its quotient units — the key keeps the cosets those units live on, the proof evaluates the quotient on them, so the two must agree on it.
 #pragma once
 #include <stdarg.h>
@@ -17,6 +17,17 @@ inline int pk_fail(zk_ctx* ctx, int code, const char* fmt, ...) {
     va_end(ap);
     return zk_internal_fail(ctx, code, buf);
 }
+
+// Advice phases and user challenges of one proof ([3P-MEM] halo2_proofs v2023_01_20 plonk/circuit.rs: advice_column_phase, challenge_phase): the key's lists (pk.hip
+// validates and keeps them) and the caller's callback and pointer array (zk_plonk_prove_phased), handed to the proof (prover.hip)
+struct PhaseSpec {
+    const uint8_t* advice_phase = nullptr;                             // n_advice entries
+    const uint8_t* challenge_phase = nullptr; uint32_t n_challenges = 0;
+    zk_phase_fn next_phase = nullptr; void* next_phase_user = nullptr;
+    const void** advice_out = nullptr;                                 // the caller's n_circuits x n_advice array: read by the proof, written by the callback
+};
+int create_proof_phased(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const PhaseSpec* ph, uint32_t n_circuits, int advice_on_device, const void* const* instances,
+                        const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len);   // prover.hip
 
 // the quotient's units of one rank (see zk_plonk_pk_desc): (coset, first row, rows).  A single GPU (world = 1) has none: parts = 1, unit_rows = n, slots = 0
 struct QuotUnits {

@@ -5,7 +5,8 @@
 // stays on the host in the reference — Fiat-Shamir hashing (transcript.h; src/transcript.rs), point encoding, rotation-set bookkeeping and the O(#points^2)
 // interpolations of SHPLONK.  zk-dcap-verifier_amd/plonk/prover.py + shplonk.py are the Python twin (phase by phase, draw by draw): `Proof` below has one member
 // function per phase of prover.py, and both must emit the bytes of the independent CPU prover's goldens (tests/test_native_prover.py).  One circuit instance or
-// several (zk_plonk_create_proof_multi: one proof over m circuits that share the key), no user challenges.  The key object (pk.hip) enters through that function only.
+// several (zk_plonk_create_proof_multi: one proof over m circuits that share the key); advice in up to three phases with user challenges between them when the key
+// carries phase lists (zk_plonk_prove_phased, PhaseSpec in plonk_shared.h).  The key object (pk.hip) enters through those two functions only.
 #include <string.h>
 #include <algorithm>
 #include <atomic>
@@ -208,11 +209,16 @@ std::vector<uint64_t> packed(const std::vector<Fe>& xs, size_t pad = 0) {
     return out;
 }
 
+// what the calling thread's last proof squeezed (zk_plonk_last_challenges): the user challenges in index order, then theta, beta, gamma, y, x, SHPLONK's y, v, u in squeeze order
+struct Squeezed { std::vector<Fe> user, rest; };
+thread_local Squeezed g_squeezed;
+Fe squeeze_noted(Transcript& tr) { const Fe c = tr.squeeze(); g_squeezed.rest.push_back(c); return c; }
+
 // ProverSHPLONK::create_proof(transcript, queries) — plonk/shplonk.py's function of the same name: `queries` in halo2's multi-open order, polynomials of n
 // coefficients on the device; `commit` commits one of them against the monomial SRS and writes the point to the transcript
 int shplonk_create_proof(zk_ctx* ctx, Arena& mem, Transcript& tr, const std::vector<Query>& queries, size_t n, const std::function<int(void*)>& commit) {
     const size_t col_bytes = n * 32;
-    const Fe one = Fr::one(), yy = tr.squeeze();
+    const Fe one = Fr::one(), yy = squeeze_noted(tr);
     // construct_intermediate_sets: commitments (by polynomial) in first-appearance order, their point sets ascending by canonical value, sets in first-appearance order
     struct Com { const void* poly; std::map<u256, Fe, CanonLess> pts; };          // canonical point -> eval
     std::vector<Com> coms;
@@ -240,7 +246,7 @@ int shplonk_create_proof(zk_ctx* ctx, Arena& mem, Transcript& tr, const std::vec
         if (si == sets.size()) sets.push_back(RSet{keys, {}});
         sets[si].members.push_back(ci);
     }
-    const Fe v = tr.squeeze();
+    const Fe v = squeeze_noted(tr);
     size_t pad = 1;
     for (auto& s : sets) pad = std::max(pad, s.keys.size());
     void* rbuf = mem.get(col_bytes);
@@ -288,7 +294,7 @@ int shplonk_create_proof(zk_ctx* ctx, Arena& mem, Transcript& tr, const std::vec
     PK(mem.take(h_x, col_bytes));
     PK(zk_fr_lincomb_dev(ctx, (const void* const*)quotients.data(), packed(vp).data(), quotients.size(), n, h_x));
     PK(commit(h_x));
-    const Fe u = tr.squeeze();
+    const Fe u = squeeze_noted(tr);
     std::vector<Fe> super_pts;
     for (auto& kv : super) super_pts.push_back(kv.second);
     std::vector<Fe> z_diffs(sets.size());
@@ -365,8 +371,9 @@ struct Proof {
     zk_ctx* const ctx; const zk_plonk_pk_desc* const pk; const uint32_t m;
     const void* const* const advice; const int advice_on_device; const void* const* const instances; const uint32_t* const instance_lens;
     const zk_rng_fn rng; void* const rng_user; void* const proof_out; const size_t proof_cap; size_t* const proof_len; ShardSignal& sig;
+    const PhaseSpec* const ph;                                         // the key's phase lists and the caller's callback (zk_plonk_prove_phased), or null: every column in phase 0, no challenge
     // sizes derived from the descriptor (validate_and_plan)
-    uint32_t k = 0, ek = 0, bf = 0, L = 0, A = 0, I = 0, chunk = 0, n_sets = 0, n_pieces = 0, world = 1, rank = 0;
+    uint32_t k = 0, ek = 0, bf = 0, L = 0, A = 0, I = 0, chunk = 0, n_sets = 0, n_pieces = 0, world = 1, rank = 0, n_phases = 1, n_chal = 0;
     size_t n = 0, en = 0, col_bytes = 0, usable = 0, n_loc = 0, shard_lo = 0, mA = 0, mI = 0, mL = 0, mS = 0, W = 0;
     bool sharded = false, by_cosets = false, side = false;
     QuotUnits qu;                                                      // the quotient's units of this rank (sharded)
@@ -381,6 +388,7 @@ struct Proof {
     size_t d_rp = 0;                                                   // ... and the random polynomial
     const Fe one = Fr::one();
     Fe theta, beta, gamma, y, x;
+    std::vector<uint64_t> chal;                                        // the user challenges, Montgomery limbs back to back (zero until squeezed); what the programs and the callback read
     // the proof's columns: m x n_advice, m x n_instance, m x n_sets, m x n_lookups (three times), circuit-major
     std::vector<Column> adv, inst, zs, lzs, pin, ptab;
     std::vector<void*> cin, ctab;                                      // compressed lookup expressions (m x n_lookups; value form only)
@@ -394,6 +402,8 @@ struct Proof {
         for (size_t i = 0; i < items.size(); i++) memcpy(&v[i * count * 4], draws.take(items[i]), count * 32);
         return v;
     }
+    uint32_t phase_of(uint32_t column) const { return ph && ph->advice_phase ? ph->advice_phase[column] : 0; }
+    const void* challenges() const { return n_chal ? (const void*)chal.data() : (const void*)one.v; }
     int fresh(Column& c) { c.owned = true; return mem.take(c.val, col_bytes); }
     static std::vector<void*> vals_of(const std::vector<Column*>& cols) { std::vector<void*> v; for (Column* c : cols) v.push_back(c->val); return v; }
     static std::vector<Column*> ptrs(std::vector<Column>& a) { std::vector<Column*> v; for (Column& c : a) v.push_back(&c); return v; }
@@ -434,7 +444,18 @@ struct Proof {
         }
         for (uint32_t i = 0; i < pk->n_advice_queries; i++) if (pk->advice_queries[2 * i] >= pk->n_advice) return ZK_ERR_ARG;
         for (uint32_t i = 0; i < pk->n_fixed_queries; i++) if (pk->fixed_queries[2 * i] >= pk->n_fixed) return ZK_ERR_ARG;
-        for (size_t i = 0; i < (size_t)m * A; i++) if (!advice[i]) return ZK_ERR_ARG;
+        // phases ([3P-MEM] plonk/circuit.rs: advice_column_phase, challenge_phase; pk.hip has validated the key's lists): later-phase entries of `advice` are the callback's to fill
+        if (ph) {
+            n_chal = ph->n_challenges;
+            for (uint32_t i = 0; i < A; i++) n_phases = std::max(n_phases, phase_of(i) + 1u);
+            if (n_phases > 1 && sharded) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_phased: a sharded key (shard_world %u): one proof over several GPUs is single-phase", world);
+            if (n_phases > 1 && !ph->next_phase) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_phased: the key has advice columns in %u phases and next_phase is NULL", n_phases);
+            for (size_t i = 0; i < (size_t)m * A && n_phases > 1; i++) if (phase_of((uint32_t)(i % A))) ph->advice_out[i] = nullptr;
+        }
+        chal.assign(4 * (size_t)std::max(n_chal, 1u), 0);
+        g_squeezed.user.clear(); g_squeezed.rest.clear();
+        g_squeezed.user.reserve(n_chal); g_squeezed.rest.reserve(8);
+        for (size_t i = 0; i < (size_t)m * A; i++) if (!phase_of((uint32_t)(i % A)) && !advice[i]) return ZK_ERR_ARG;
         if (pk->transcript > 2) return ZK_ERR_ARG;
         tr.kind = (int)pk->transcript;
         // exchange buffers of a sharded proof: the caller's (e.g. two torch tensors, so that its callback can hand RCCL tensors) or the proof's own.  First thing of all:
@@ -457,13 +478,16 @@ struct Proof {
         // vanishing argument's n coefficients + one Blind; one Blind per h(X) piece.
         if (pk->draw_schedule != 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof: draw_schedule %u (1 = halo2_proofs v2023_01_20, the only schedule this build knows)", pk->draw_schedule);
         // m circuits: each per-circuit block below runs for circuit 0, 1, .., m-1 in turn (circuit c + 1's advice draws start after circuit c's Blinds); the vanishing argument once.
+        // Advice phases: the advice block runs phase-major — per phase, per circuit, the rows of that phase's columns and then their Blinds.  No draw depends on a challenge,
+        // so the helper thread still makes them all ahead of the phases.
         mA = (size_t)m * A; mI = (size_t)m * I; mL = (size_t)m * L; mS = (size_t)m * n_sets;
         W = (size_t)A + I + n_sets + 3 * (size_t)L;
         d_ar.resize(mA); d_bi.resize(mL); d_bt.resize(mL); d_pb.resize(mS); d_lb.resize(mL);
-        for (uint32_t c = 0; c < m; c++) {
-            for (uint32_t i = 0; i < A; i++) d_ar[(size_t)c * A + i] = plan(n - usable);                // (m = 1: items [0, n_advice))
-            for (uint32_t i = 0; i < A; i++) plan(1);
-        }
+        for (uint32_t p = 0; p < n_phases; p++)
+            for (uint32_t c = 0; c < m; c++) {
+                for (uint32_t i = 0; i < A; i++) if (phase_of(i) == p) d_ar[(size_t)c * A + i] = plan(n - usable);      // (m = 1, one phase: items [0, n_advice))
+                for (uint32_t i = 0; i < A; i++) if (phase_of(i) == p) plan(1);
+            }
         for (size_t cl = 0; cl < mL; cl++) { d_bi[cl] = plan(bf + 1); d_bt[cl] = plan(bf + 1); plan(1); plan(1); }
         for (size_t cs = 0; cs < mS; cs++) { d_pb[cs] = plan(bf); plan(1); }
         for (size_t cl = 0; cl < mL; cl++) { d_lb[cl] = plan(bf); plan(1); }
@@ -545,28 +569,62 @@ struct Proof {
         }
         return ZK_OK;
     }
-    // ---- 2. advice: upload (host columns), blind, commit ------------------------------------------------------------------------------------------------
+    // ---- 2. advice, phase by phase: upload (host columns), blind, commit, squeeze the phase's challenges ---------------------------------------------------
+    // the columns of advice phase p, circuit-major, ascending index within a circuit: halo2's commitment order ([3P-MEM] plonk/prover.rs)
+    std::vector<Column*> phase_columns(uint32_t p) {
+        std::vector<Column*> v;
+        for (uint32_t c = 0; c < m; c++) for (uint32_t i = 0; i < A; i++) if (phase_of(i) == p) v.push_back(&adv[(size_t)c * A + i]);
+        return v;
+    }
+    // the caller synthesises phase p with the challenges known so far (zk_phase_fn): on this thread, between two library calls — no lock of the library is held, and the
+    // side lane goes on transforming the columns of the phases before
+    int next_phase_columns(uint32_t p) {
+        const int r = ph->next_phase(ph->next_phase_user, p, chal.data(), n_chal, ph->advice_out);
+        if (r) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_phased: the caller's callback returned %d for phase %u", r, p);
+        for (uint32_t c = 0; c < m; c++)
+            for (uint32_t i = 0; i < A; i++)
+                if (phase_of(i) == p && !advice[(size_t)c * A + i])
+                    return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_phased: the caller's callback left advice column %u of circuit %u NULL in phase %u", i, c, p);
+        return ZK_OK;
+    }
+    int advice_phase(uint32_t p) {
+        const std::vector<Column*> cols = phase_columns(p);
+        std::vector<void*> dst, bdst;
+        std::vector<const void*> src, bsrc;
+        for (uint32_t c = 0; c < m; c++)
+            for (uint32_t i = 0; i < A; i++) {
+                if (phase_of(i) != p) continue;
+                const size_t at = (size_t)c * A + i;
+                if (advice_on_device) adv[at].val = (void*)advice[at];
+                else { PK(fresh(adv[at])); dst.push_back(adv[at].val); src.push_back(advice[at]); }
+                bdst.push_back((char*)adv[at].val + usable * 32); bsrc.push_back(draws.take(d_ar[at]));
+            }
+        if (!dst.empty()) PK(zk_dev_upload_batch(ctx, dst.data(), src.data(), dst.size(), col_bytes));
+        if (!bdst.empty()) PK(zk_dev_upload_batch(ctx, bdst.data(), bsrc.data(), bdst.size(), (n - usable) * 32));
+        if (side) {
+            std::vector<Column*> final_now = cols;
+            if (!p) { const std::vector<Column*> in = ptrs(inst); final_now.insert(final_now.end(), in.begin(), in.end()); }
+            PK(early(final_now));
+        }
+        PK(commit(pk->srs_g_lagrange, vals_of(cols)));                     // (one batch: the phase's commitments of all m circuits, circuit by circuit in the transcript)
+        for (uint32_t i = 0; i < n_chal; i++)
+            if (ph->challenge_phase[i] == p) { const Fe c = tr.squeeze(); memcpy(&chal[4 * (size_t)i], c.v, 32); }
+        return ZK_OK;
+    }
     int advice_columns() {
         adv.resize(mA);
-        std::vector<void*> dst;
-        std::vector<const void*> src;
-        for (size_t i = 0; i < mA; i++) {
-            if (advice_on_device) adv[i].val = (void*)advice[i];
-            else { PK(fresh(adv[i])); dst.push_back(adv[i].val); src.push_back(advice[i]); }
-        }
-        if (!dst.empty()) PK(zk_dev_upload_batch(ctx, dst.data(), src.data(), dst.size(), col_bytes));
-        std::vector<void*> bdst(mA);
-        std::vector<const void*> bsrc(mA);
-        for (size_t i = 0; i < mA; i++) { bdst[i] = (char*)adv[i].val + usable * 32; bsrc[i] = draws.take(d_ar[i]); }
-        if (mA) PK(zk_dev_upload_batch(ctx, bdst.data(), bsrc.data(), mA, (n - usable) * 32));
         // the side lane (SideLane above): a single-GPU proof on the extended domain hands every phase's columns to the helper context as soon as their values are final
         int want = 0;
         if (!sharded && !by_cosets && zk_tune_get(ctx, "prover_side_lane", &want) == ZK_OK && (want >= 2 || (want == 1 && g_proofs_in_flight.load() <= 2))) {
             zk_ctx* h = zk_internal_helper_ctx(ctx);
             if (h) { try { lane.start(h); side = true; } catch (const std::system_error&) { side = false; } }      // no thread to be had: the proof runs in one lane, as with three proofs in flight
         }
-        if (side) PK(early(ptrs(adv, inst)));
-        return commit(pk->srs_g_lagrange, vals_of(ptrs(adv)));             // (one batch: the m x n_advice commitments, circuit by circuit in the transcript)
+        for (uint32_t p = 0; p < n_phases; p++) {
+            if (p) PK(next_phase_columns(p));
+            PK(advice_phase(p));
+        }
+        for (uint32_t i = 0; i < n_chal; i++) { Fe c; memcpy(c.v, &chal[4 * (size_t)i], 32); g_squeezed.user.push_back(c); }
+        return ZK_OK;
     }
     // one lookup expression of circuit c, compressed with theta (a ZKQ1 program of its own over the circuit's value forms)
     int compress(uint32_t c, uint64_t prog, void*& out) {
@@ -579,13 +637,13 @@ struct Proof {
         ZK_STRUCT_INIT(a);
         a.fixed = pk->fixed_values; a.advice = a_vals.data(); a.instance = i_vals.data();
         a.l0 = a.l_last = a.l_active_row = anycol;
-        a.beta = a.gamma = a.y = one.v; a.theta = theta.v; a.challenges = one.v;
+        a.beta = a.gamma = a.y = one.v; a.theta = theta.v; a.challenges = challenges();
         a.out = out;
         return zk_quotient_run_dev(ctx, prog, &a);
     }
     // ---- 3. theta; lookups: compress, permute, commit ---------------------------------------------------------------------------------------------------
     int lookups() {
-        theta = tr.squeeze();
+        theta = squeeze_noted(tr);
         cin.resize(mL); ctab.resize(mL); pin.resize(mL); ptab.resize(mL);
         std::map<std::pair<uint32_t, uint32_t>, void*> table_cache;     // (circuit, table key): a table expression may read the circuit's own columns
         for (uint32_t c = 0; c < m; c++)
@@ -607,7 +665,7 @@ struct Proof {
     }
     // ---- 4. beta, gamma; grand products -------------------------------------------------------------------------------------------------------------------
     int grand_products() {
-        beta = tr.squeeze(); gamma = tr.squeeze();
+        beta = squeeze_noted(tr); gamma = squeeze_noted(tr);
         zs.resize(mS); lzs.resize(mL);
         if (n_sets) {
             std::vector<const void*> vals((size_t)m * pk->n_perm_columns);
@@ -650,7 +708,7 @@ struct Proof {
         a.advice = (const void* const*)cols; a.instance = (const void* const*)cols + A;
         a.perm_products = (const void* const*)cols + A + I; a.n_sets = n_sets;
         a.lookup_product = (const void* const*)cols + A + I + n_sets; a.lookup_input = e_in.data(); a.lookup_table = e_tab.data();
-        a.challenges = one.v; a.beta = beta.v; a.gamma = gamma.v; a.theta = theta.v; a.y = y.v;
+        a.challenges = challenges(); a.beta = beta.v; a.gamma = gamma.v; a.theta = theta.v; a.y = y.v;
         a.fixed = whole ? pk->fixed_cosets : pk->coset_fixed + key_at * pk->n_fixed;
         a.perm_cosets = whole ? pk->sigma_cosets : pk->coset_sigma + key_at * pk->n_perm_columns;
         a.l0 = whole ? pk->l0 : pk->coset_l[3 * key_at]; a.l_last = whole ? pk->l_last : pk->coset_l[3 * key_at + 1]; a.l_active_row = whole ? pk->l_active_row : pk->coset_l[3 * key_at + 2];
@@ -662,7 +720,7 @@ struct Proof {
     }
     // ---- 6. y; coefficient form; extended cosets; h(X) numerator ----------------------------------------------------------------------------------------------
     int quotient() {
-        y = tr.squeeze();
+        y = squeeze_noted(tr);
         // the proof's columns, one block of W per circuit in the order the quotient's arguments take them: advice, instance, permutation products, lookup products, permuted pairs
         std::vector<Column*> cols;
         for (uint32_t c = 0; c < m; c++) {
@@ -778,7 +836,7 @@ struct Proof {
     // in halo2's multi-open order as `open` = (section, place in it): per circuit c its advice (4c), permutation x / x_next (4c + 1), permutation x_last from the last set
     // down (4c + 2), lookup queries in lookup::Evaluated::open order (4c + 3); then fixed, sigma, h, the random polynomial once (4m ..).  multi_open sorts by it.
     int evaluations() {
-        x = tr.squeeze();
+        x = squeeze_noted(tr);
         Fe xn = x;
         for (uint32_t i = 0; i < k; i++) xn = Fr::sqr(xn);
         Fe omega;
@@ -853,14 +911,14 @@ struct Proof {
 }  // namespace
 
 static int create_proof_entry(zk_ctx* ctx, const zk_plonk_pk_desc* pk, uint32_t m, const void* const* advice, int advice_on_device, const void* const* instances,
-                              const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) {
+                              const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len, const PhaseSpec* ph = nullptr) {
     if (!ctx || !pk) return ZK_ERR_ARG;
     InFlight counted;
     Arena xmem(ctx);                                                   // (before the proof's own arena: a failing proof has returned everything else when the poisoned block travels)
     ShardSignal sig;
     sig.xmem = &xmem;
     int rc;
-    try { Proof proof{ctx, pk, m, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len, sig}; rc = proof.run(); }
+    try { Proof proof{ctx, pk, m, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len, sig, ph}; rc = proof.run(); }
     catch (...) { rc = abi_exception(ctx, "zk_plonk_create_proof"); }   // (here rather than at the barrier below: the other ranks of a sharded proof are told first)
     if (rc != ZK_OK && rc != ZK_ERR_COMM && sig.armed && sig.next < sig.sizes.size()) {
         std::string why = zk_last_error(ctx) ? zk_last_error(ctx) : "";
@@ -884,6 +942,26 @@ extern "C" int zk_plonk_create_proof_multi(zk_ctx* ctx, const zk_plonk_pk_desc* 
     if (!n_circuits) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof_multi: n_circuits = 0");
     return create_proof_entry(ctx, pk, n_circuits, advice, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len);
 } ZK_ABI_CATCH(ctx)
+
+// zk_plonk_prove_phased (pk.hip) with the key's descriptor and phase lists: the barrier is the caller's
+int zk::create_proof_phased(zk_ctx* ctx, const zk_plonk_pk_desc* pk, const PhaseSpec* ph, uint32_t n_circuits, int advice_on_device, const void* const* instances,
+                            const uint32_t* instance_lens, zk_rng_fn rng, void* rng_user, void* proof_out, size_t proof_cap, size_t* proof_len) {
+    if (!ctx || !pk || !ph) return ZK_ERR_ARG;
+    if (!n_circuits) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_prove_phased: n_circuits = 0");
+    if (pk->n_advice && !ph->advice_out) return ZK_ERR_ARG;
+    return create_proof_entry(ctx, pk, n_circuits, ph->advice_out, advice_on_device, instances, instance_lens, rng, rng_user, proof_out, proof_cap, proof_len, ph);
+}
+
+extern "C" int zk_plonk_last_challenges(void* out, size_t cap, size_t* n) ZK_ABI_TRY {
+    if (!n) return ZK_ERR_ARG;
+    const size_t count = g_squeezed.user.size() + g_squeezed.rest.size();
+    *n = count;
+    if (cap < count * 32 || (count && !out)) return ZK_ERR_LIMIT;
+    size_t at = 0;
+    for (const std::vector<Fe>* part : {&g_squeezed.user, &g_squeezed.rest})
+        for (const Fe& c : *part) { const u256 canon = Fr::from_mont(c); memcpy((char*)out + 32 * at++, canon.v, 32); }
+    return ZK_OK;
+} ZK_ABI_CATCH(nullptr)
 
 extern "C" int zk_plonk_last_phase_ms(double out[9]) ZK_ABI_TRY {
     if (!out) return ZK_ERR_ARG;

@@ -5,6 +5,7 @@ circuits/src/sgx_dcap_verifier.rs:803,807,814-822), as a host-side mirror over t
     keygen(params, cs, fixed_columns, assembly) -> ProvingKey                            keygen_vk + keygen_pk
     create_proof(params, pk, advice_columns, instances, rng, transcript)                 plonk::create_proof + ProverSHPLONK (Python twin; multi-GPU driver)
     NativeProver(params, pk).create_proof(advice_columns, instances, rng) -> bytes       the same per-proof path in C++ (zk_plonk_create_proof)
+    PhasedProver(params, pk).create_proof(advices, instances, rng, next_phase) -> bytes  advice in phases with halo2's Challenge API (zk_plonk_prove_phased)
     MockProver.run(k, cs, fixed, advice, instances, assembly).assert_satisfied()         dev::MockProver (host-only constraint check)
     NativeMockProver.run(k, cs, fixed, advice, instances, assembly).assert_satisfied()   the same check on the GPU (zk_mock_prover_verify)
 
@@ -13,8 +14,8 @@ pure-Python verifier as the acceptance check, outside this package.
 """
 from .circuit import ADVICE, FIXED, INSTANCE, Assembly, ConstraintSystem, LookupArgument  # noqa: F401
 from .dev import MockProver, NativeMockProver, VerifyFailure  # noqa: F401
-from .expression import Advice, Constant, Expression, Fixed, Instance  # noqa: F401
-from .keygen import ProvingKey, VerifyingKey, compile_program, keygen  # noqa: F401
+from .expression import Advice, Challenge, Constant, Expression, Fixed, Instance  # noqa: F401
+from .keygen import NativeKey, ProvingKey, VerifyingKey, compile_program, keygen  # noqa: F401
 from .prover import create_proof  # noqa: F401
-from .native import NativeProver, create_proof_native  # noqa: F401
+from .native import NativeProver, PhasedProver, create_proof_native, last_challenges  # noqa: F401
 from .shplonk import ProverSHPLONK  # noqa: F401

@@ -40,6 +40,44 @@ class ConstraintSystem:
     lookups: List[LookupArgument] = field(default_factory=list)
     permutation_columns: List[Tuple[int, int]] = field(default_factory=list)   # (column_type, index) — enable_equality order
     minimum_degree: int = 1
+    # multi-phase advice and the Challenge API ([3P-MEM] halo2_proofs v2023_01_20 plonk/circuit.rs): the phase of every advice column (columns counted through
+    # num_advice_columns alone are in phase 0) and the phase after which every challenge is squeezed
+    advice_column_phase: List[int] = field(default_factory=list)
+    challenge_phase: List[int] = field(default_factory=list)
+
+    def _advice_phases(self) -> List[int]:
+        return list(self.advice_column_phase) + [0] * (self.num_advice_columns - len(self.advice_column_phase))
+
+    @property
+    def num_challenges(self) -> int:
+        return len(self.challenge_phase)
+
+    def phases(self) -> List[int]:
+        """the phases in use: 0 ..= the highest phase of an advice column"""
+        return list(range(max([0] + self._advice_phases()) + 1))
+
+    def is_phased(self) -> bool:
+        return len(self.phases()) > 1 or self.num_challenges > 0
+
+    def _check_phase(self, phase: int, what: str) -> None:
+        if not 0 <= phase <= 2:
+            raise ValueError(f"{what}: phase {phase} (0 .. 2)")
+        if phase > 0 and (phase - 1) not in self._advice_phases():       # halo2 panics: "No Column<Advice> is used in phase .. while allocating a new .. in phase .."
+            raise ValueError(f"{what}: phase {phase} while no advice column is in phase {phase - 1}")
+
+    def advice_column_in(self, phase: int) -> int:
+        """ConstraintSystem::advice_column_in: a new advice column in `phase`; returns its index"""
+        self._check_phase(phase, "advice_column_in")
+        self.advice_column_phase = self._advice_phases() + [phase]
+        self.num_advice_columns += 1
+        return self.num_advice_columns - 1
+
+    def challenge_usable_after(self, phase: int) -> "ex.Challenge":
+        """ConstraintSystem::challenge_usable_after: a challenge squeezed after the commitments of `phase`, which must be a phase in use"""
+        if not 0 <= phase <= 2 or phase not in self._advice_phases():
+            raise ValueError(f"challenge_usable_after: no advice column is in phase {phase}")
+        self.challenge_phase = list(self.challenge_phase) + [phase]
+        return ex.Challenge(len(self.challenge_phase) - 1)
 
     # -- construction (ConstraintSystem::{create_gate, lookup, enable_equality}) -------------------------------------
     # halo2 records a column query the moment `meta.query_*` runs, i.e. in CALL order across create_gate / lookup / enable_equality

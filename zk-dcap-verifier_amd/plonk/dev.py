@@ -20,27 +20,30 @@ class VerifyFailure(Exception):
 
 
 class MockProver:
-    def __init__(self, k: int, cs: ConstraintSystem, fixed: Sequence, advice: Sequence, instances: Sequence[Sequence[int]], assembly: Assembly | None = None):
+    def __init__(self, k: int, cs: ConstraintSystem, fixed: Sequence, advice: Sequence, instances: Sequence[Sequence[int]], assembly: Assembly | None = None,
+                 challenges: Sequence[int] | None = None):
         self.k, self.n, self.cs, self.assembly = k, 1 << k, cs, assembly
+        self.challenges = None if challenges is None else [int(c) % R_MOD for c in challenges]     # the values of cs's user challenges (halo2's MockProver derives its own)
         conv = lambda c: [int(v) % R_MOD for v in c] if not hasattr(c, "dtype") else fr_int_array(c)
         self.fixed = [conv(c) for c in fixed]
         self.advice = [conv(c) for c in advice]
         self.instance = [list(c) + [0] * (self.n - len(c)) for c in instances]
 
     @classmethod
-    def run(cls, k, cs, fixed, advice, instances, assembly=None) -> "MockProver":
-        return cls(k, cs, fixed, advice, instances, assembly)
+    def run(cls, k, cs, fixed, advice, instances, assembly=None, challenges=None) -> "MockProver":
+        return cls(k, cs, fixed, advice, instances, assembly, challenges)
 
     def verify(self) -> List[str]:
         cs, n = self.cs, self.n
         u = cs.usable_rows(self.k)
         failures: List[str] = []
+        ch = None if self.challenges is None else (lambda i: self.challenges[i])
         for row in range(u):
             fx = lambda c, r, row=row: self.fixed[c][(row + r) % n]
             ad = lambda c, r, row=row: self.advice[c][(row + r) % n]
             ins = lambda c, r, row=row: self.instance[c][(row + r) % n]
             for gi, g in enumerate(cs.gates):
-                if ex.evaluate(g, fx, ad, ins) != 0:
+                if ex.evaluate(g, fx, ad, ins, ch) != 0:
                     failures.append(f"gate {gi} not satisfied on row {row}")
         for li, lk in enumerate(cs.lookups):
             rows = []
@@ -48,8 +51,8 @@ class MockProver:
                 fx = lambda c, r, row=row: self.fixed[c][(row + r) % n]
                 ad = lambda c, r, row=row: self.advice[c][(row + r) % n]
                 ins = lambda c, r, row=row: self.instance[c][(row + r) % n]
-                rows.append((tuple(ex.evaluate(e, fx, ad, ins) for e in lk.input_expressions),
-                             tuple(ex.evaluate(e, fx, ad, ins) for e in lk.table_expressions)))
+                rows.append((tuple(ex.evaluate(e, fx, ad, ins, ch) for e in lk.input_expressions),
+                             tuple(ex.evaluate(e, fx, ad, ins, ch) for e in lk.table_expressions)))
             table = {t for _, t in rows}
             for row, (inp, _) in enumerate(rows):
                 if inp not in table:
@@ -79,12 +82,12 @@ class NativeMockProver:
     all 2^k rows and returns MockProver.verify()'s failures in MockProver.verify()'s order.  Built from what keygen builds: the Evaluator's ZKQ1 blob
     (keygen.compile_program; only its custom gates are read), the lookup compressor programs, and Assembly.map_c / map_r as the copy mapping.
     Gates and lookups are detected through random folds the library draws per call (a failure is missed with probability at most E / |Fr|
-    for E gate polynomials, (m - 1) / |Fr| for a lookup tuple of m expressions); single-phase circuits only, as the native prover."""
+    for E gate polynomials, (m - 1) / |Fr| for a lookup tuple of m expressions).  A circuit with user challenges takes their values as `challenges` (zk_mock_prover_verify_phased)."""
 
     KINDS = ("gate", "lookup", "copy")
 
     def __init__(self, k: int, cs: ConstraintSystem, fixed: Sequence, advice: Sequence, instances: Sequence[Sequence[int]], assembly: Assembly | None = None,
-                 backend=None):
+                 backend=None, challenges: Sequence[int] | None = None):
         from .._lib import default_backend
         from .keygen import compile_program, compressor_program
         self.k, self.n, self.cs, self.assembly = k, 1 << k, cs, assembly
@@ -104,11 +107,13 @@ class NativeMockProver:
                          lookup_table_blobs=[compressor_program(cs, k, lk.table_expressions).to_blob() for lk in cs.lookups],
                          fixed=self.fixed, advice=self.advice, instances=self.instances,
                          perm_map_column=assembly.map_c if perm else None, perm_map_row=assembly.map_r if perm else None)
+        if challenges is not None:
+            self.args["challenges"] = [int(c) % R_MOD for c in challenges]
         self._records, self._counts = None, None
 
     @classmethod
-    def run(cls, k, cs, fixed, advice, instances, assembly=None, backend=None) -> "NativeMockProver":
-        return cls(k, cs, fixed, advice, instances, assembly, backend)
+    def run(cls, k, cs, fixed, advice, instances, assembly=None, backend=None, challenges=None) -> "NativeMockProver":
+        return cls(k, cs, fixed, advice, instances, assembly, backend, challenges)
 
     def _check(self, cap: int):
         recs, counts = self.backend.mock_prover_verify(cap=cap, **self.args)

@@ -55,6 +55,11 @@ class Instance(Expression):
     rotation: int = 0
 
 @dataclass(frozen=True, eq=True)
+class Challenge(Expression):
+    """Expression::Challenge ([3P-MEM] halo2_proofs v2023_01_20 plonk/circuit.rs): a value squeezed after an advice phase; degree 0, no query"""
+    index: int
+
+@dataclass(frozen=True, eq=True)
 class Negated(Expression):
     a: Expression
 
@@ -76,7 +81,7 @@ class Scaled(Expression):
 
 def degree(e: Expression) -> int:
     """Expression::degree."""
-    if isinstance(e, Constant):
+    if isinstance(e, (Constant, Challenge)):
         return 0
     if isinstance(e, (Fixed, Advice, Instance)):
         return 1
@@ -106,9 +111,10 @@ def queries(e: Expression, out: dict) -> None:
         queries(e.b, out)
 
 
-def evaluate(e: Expression, fixed, advice, instance) -> int:
-    """Expression::evaluate over canonical ints; fixed/advice/instance: callables (column, rotation) -> int.
-    (Host use: the verifier's gate check and small-k witness checks; never bulk data.)"""
+def evaluate(e: Expression, fixed, advice, instance, challenge=None) -> int:
+    """Expression::evaluate over canonical ints; fixed/advice/instance: callables (column, rotation) -> int; challenge: callable index -> int
+    (needed only by an expression that holds a Challenge).  (Host use: the verifier's gate check and small-k witness checks; never bulk data.)"""
+    sub = lambda t: evaluate(t, fixed, advice, instance, challenge)
     if isinstance(e, Constant):
         return e.value % R_MOD
     if isinstance(e, Fixed):
@@ -117,14 +123,18 @@ def evaluate(e: Expression, fixed, advice, instance) -> int:
         return advice(e.column, e.rotation)
     if isinstance(e, Instance):
         return instance(e.column, e.rotation)
+    if isinstance(e, Challenge):
+        if challenge is None:
+            raise ValueError("Expression::Challenge evaluated without challenge values")
+        return challenge(e.index) % R_MOD
     if isinstance(e, Negated):
-        return (-evaluate(e.a, fixed, advice, instance)) % R_MOD
+        return (-sub(e.a)) % R_MOD
     if isinstance(e, Sum):
-        return (evaluate(e.a, fixed, advice, instance) + evaluate(e.b, fixed, advice, instance)) % R_MOD
+        return (sub(e.a) + sub(e.b)) % R_MOD
     if isinstance(e, Product):
-        return evaluate(e.a, fixed, advice, instance) * evaluate(e.b, fixed, advice, instance) % R_MOD
+        return sub(e.a) * sub(e.b) % R_MOD
     if isinstance(e, Scaled):
-        return evaluate(e.a, fixed, advice, instance) * e.f % R_MOD
+        return sub(e.a) * e.f % R_MOD
     raise TypeError(e)
 
 
@@ -167,6 +177,8 @@ class GraphBuilder:
             return self.add_calculation(ev.STORE, ev.vs(ev.ADVICE, e.column, self.add_rotation(e.rotation)))
         if isinstance(e, Instance):
             return self.add_calculation(ev.STORE, ev.vs(ev.INSTANCE, e.column, self.add_rotation(e.rotation)))
+        if isinstance(e, Challenge):                            # value source 5 (ZKQ1), stored like a query
+            return self.add_calculation(ev.STORE, ev.vs(ev.CHALLENGE, e.index))
         if isinstance(e, Negated):
             if isinstance(e.a, Constant):
                 return self.add_constant(-e.a.value)

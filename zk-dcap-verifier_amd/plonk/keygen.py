@@ -114,7 +114,7 @@ def compile_program(cs: ConstraintSystem, k: int, extended_k: int) -> ev.Program
         lb.add_calculation(ev.MUL, left, right)
         lookups.append(lb.graph)
     return ev.Program(k=k, extended_k=extended_k, n_fixed=cs.num_fixed_columns, n_advice=cs.num_advice_columns,
-                      n_instance=cs.num_instance_columns, n_challenges=0, blinding_factors=cs.blinding_factors(), cs_degree=cs.degree(),
+                      n_instance=cs.num_instance_columns, n_challenges=cs.num_challenges, blinding_factors=cs.blinding_factors(), cs_degree=cs.degree(),
                       perm_columns=list(cs.permutation_columns), custom_gates=gb.graph, lookups=lookups)
 
 
@@ -123,11 +123,91 @@ def compressor_program(cs: ConstraintSystem, k: int, exprs) -> ev.Program:
     gb = GraphBuilder()
     ps = [gb.add_expression(e) for e in exprs]
     gb.add_calculation(ev.HORNER, ev.vs(ev.CONSTANT, 0), ps, ev.vs(ev.THETA))
-    return ev.expression_program(k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, 0, gb.graph)
+    return ev.expression_program(k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, cs.num_challenges, gb.graph)
 
 
 def _compressor(cs: ConstraintSystem, k: int, exprs, be: Backend) -> ev.Evaluator:
     return ev.Evaluator(compressor_program(cs, k, exprs), backend=be)
+
+
+class NativeKey:
+    """The library's own proving-key object for `pk` (zk_plonk_pk_build_phased, csrc/pk.hip): built from the Lagrange columns keygen left on the device (borrowed: `pk` must
+    outlive it), the ZKQ1 blobs and the circuit's phase lists.  What a Rust or C caller holds instead of a ProvingKey; plonk.native.PhasedProver proves with it."""
+
+    def __init__(self, params: ParamsKZG, pk: "ProvingKey", transcript: int = 0):
+        import ctypes as C
+        from .._lib import PlonkPhases, _dptr
+        from .native import PkHost
+        be, cs = pk.backend, pk.vk.cs
+        assert params.world == 1, "one proof over several GPUs is single-phase (zk_plonk_pk_build_phased refuses shard_world > 1)"
+        keep = []
+
+        def u32(vals):
+            a = np.ascontiguousarray(np.asarray(vals, dtype=np.int64).astype(np.uint32).reshape(-1))
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        def ptrs(vals):
+            arr = (C.c_void_p * max(1, len(vals)))(*vals)
+            keep.append(arr)
+            return C.cast(arr, C.c_void_p).value
+
+        def blobs(programs):
+            bufs = [(C.c_char * len(b)).from_buffer_copy(b) for b in (p.to_blob() for p in programs)]
+            keep.extend(bufs)
+            lens = (C.c_size_t * max(1, len(bufs)))(*[len(b) for b in bufs])
+            keep.append(lens)
+            return ptrs([C.addressof(b) for b in bufs]), C.cast(lens, C.c_void_p).value
+        keys, key_ids = {}, []
+        for lk in cs.lookups:
+            key_ids.append(keys.setdefault(tuple(lk.table_expressions), len(keys)))
+        h = PkHost()
+        h.struct_size = C.sizeof(PkHost)
+        h.k, h.cs_degree, h.blinding_factors = params.k, cs.degree(), cs.blinding_factors()
+        h.n_fixed, h.n_advice, h.n_instance = cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns
+        h.n_lookups, h.n_perm_columns = len(cs.lookups), len(cs.permutation_columns)
+        h.perm_columns = u32([v for t, i in cs.permutation_columns for v in (t, i)])
+        aq, fq = cs.advice_queries(), cs.fixed_queries()
+        h.advice_queries, h.n_advice_queries = u32([v for c, r in aq for v in (c, r)]), len(aq)
+        h.fixed_queries, h.n_fixed_queries = u32([v for c, r in fq for v in (c, r)]), len(fq)
+        ev_blob = (C.c_char * len(pk.program.to_blob())).from_buffer_copy(pk.program.to_blob())
+        keep.append(ev_blob)
+        h.evaluator_zkq1, h.evaluator_zkq1_len = C.addressof(ev_blob), len(ev_blob)
+        h.lookup_input_zkq1, h.lookup_input_zkq1_len = blobs([a.program for a, _ in pk.lookup_compressors])
+        h.lookup_table_zkq1, h.lookup_table_zkq1_len = blobs([b.program for _, b in pk.lookup_compressors])
+        h.lookup_table_key = u32(key_ids)
+        h.fixed_values, h.sigma_values, h.values_on_device = ptrs([_dptr(d) for d in pk.fixed_values]), ptrs([_dptr(d) for d in pk.sigma_values]), 1
+        repr_bytes = np.frombuffer(int(pk.vk.transcript_repr).to_bytes(32, "little"), dtype=np.uint8).copy()
+        keep.append(repr_bytes)
+        h.transcript_repr, h.transcript, h.draw_schedule = repr_bytes.ctypes.data, transcript, 1
+        ph = PlonkPhases()
+        ph.struct_size = C.sizeof(PlonkPhases)
+        ap = np.asarray(cs._advice_phases(), dtype=np.uint8)
+        cp = np.asarray(cs.challenge_phase, dtype=np.uint8)
+        keep += [ap, cp]
+        ph.n_advice, ph.advice_phase = len(ap), ap.ctypes.data if ap.size else None
+        ph.n_challenges, ph.challenge_phase = len(cp), cp.ctypes.data if cp.size else None
+        self.host, self.phases, self._keep = h, ph, keep               # (kept: tests rebuild with altered copies)
+        self.backend, self.pk = be, pk
+        out = C.c_uint64()
+        be._ck(be.lib.zk_plonk_pk_build_phased(be.ctx, C.byref(h), C.byref(ph), C.c_uint64(params.g.handle), C.c_uint64(params.g_lagrange.handle), C.byref(out)))
+        self.handle = out.value
+
+    def shared_with(self, backend, params: ParamsKZG) -> "NativeKey":
+        """the same key for another context of the same GPU (zk_plonk_pk_share); `params` is that context's SRS"""
+        import ctypes as C
+        other = NativeKey.__new__(NativeKey)
+        other.host, other.phases, other._keep, other.backend, other.pk = self.host, self.phases, self._keep, backend, self.pk
+        out = C.c_uint64()
+        backend._ck(backend.lib.zk_plonk_pk_share(backend.ctx, self.backend.ctx, C.c_uint64(self.handle), C.c_uint64(params.g.handle), C.c_uint64(params.g_lagrange.handle), C.byref(out)))
+        other.handle = out.value
+        return other
+
+    def release(self):
+        import ctypes as C
+        if self.handle:
+            self.backend._ck(self.backend.lib.zk_plonk_pk_release(self.backend.ctx, C.c_uint64(self.handle)))
+            self.handle = 0
 
 
 def _as_mont(col, n) -> np.ndarray:
@@ -179,6 +259,8 @@ def keygen(params: ParamsKZG, cs: ConstraintSystem, fixed_columns, assembly: Opt
     h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
     h.update(repr((k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, len(cs.gates), len(cs.lookups),
                    cs.permutation_columns, cs.degree(), fixed_commitments, permutation_commitments)).encode())
+    if cs.is_phased():                                                   # (halo2's pinned vk renders advice_column_phase / challenge_phase too; single-phase circuits keep their bytes)
+        h.update(repr(("phases", cs._advice_phases(), list(cs.challenge_phase))).encode())
     vk = VerifyingKey(k, cs, fixed_commitments, permutation_commitments, int.from_bytes(h.digest(), "little") % R_MOD)
 
     # keygen_pk: polys and extended cosets (when the quotient is sharded: only this rank's cosets, 2^k values each)

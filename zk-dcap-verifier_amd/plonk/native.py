@@ -12,7 +12,7 @@ from typing import Sequence
 
 import numpy as np
 
-from .._lib import _dptr
+from .._lib import PHASE_FN, _dptr
 from ..fields import rand_fr_array
 from ..kzg import ParamsKZG
 from .keygen import ProvingKey
@@ -72,6 +72,112 @@ class PkDesc(C.Structure):
                 ("shard_world", C.c_uint32), ("shard_rank", C.c_uint32), ("allgather", ALLGATHER_FN), ("allgather_user", C.c_void_p),
                 ("xchg_send", C.c_void_p), ("xchg_recv", C.c_void_p), ("xchg_cap", C.c_size_t),
                 ("coset_fixed", C.c_void_p), ("coset_sigma", C.c_void_p), ("coset_l", C.c_void_p)]
+
+
+class PkHost(C.Structure):
+    """zk_plonk_pk_host (zk_plonk_pk_build / zk_plonk_pk_build_phased)"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("cs_degree", C.c_uint32), ("blinding_factors", C.c_uint32),
+                ("n_fixed", C.c_uint32), ("n_advice", C.c_uint32), ("n_instance", C.c_uint32), ("n_lookups", C.c_uint32), ("n_perm_columns", C.c_uint32),
+                ("perm_columns", C.c_void_p),
+                ("advice_queries", C.c_void_p), ("n_advice_queries", C.c_uint32),
+                ("fixed_queries", C.c_void_p), ("n_fixed_queries", C.c_uint32),
+                ("evaluator_zkq1", C.c_void_p), ("evaluator_zkq1_len", C.c_size_t),
+                ("lookup_input_zkq1", C.c_void_p), ("lookup_input_zkq1_len", C.c_void_p),
+                ("lookup_table_zkq1", C.c_void_p), ("lookup_table_zkq1_len", C.c_void_p),
+                ("lookup_table_key", C.c_void_p),
+                ("fixed_values", C.c_void_p), ("sigma_values", C.c_void_p), ("values_on_device", C.c_uint32),
+                ("transcript_repr", C.c_void_p), ("transcript", C.c_uint32), ("draw_schedule", C.c_uint32),
+                ("shard_world", C.c_uint32), ("shard_rank", C.c_uint32), ("allgather", ALLGATHER_FN), ("allgather_user", C.c_void_p)]
+
+
+def last_challenges(be, cap: int = 64) -> list:
+    """zk_plonk_last_challenges: what the calling thread's last native proof squeezed, canonical ints — the user challenges, then theta, beta, gamma, y, x, SHPLONK's y, v, u"""
+    out = np.zeros(32 * cap, dtype=np.uint8)
+    n = C.c_size_t()
+    be._ck(be.lib.zk_plonk_last_challenges(out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes), C.byref(n)))
+    return [int.from_bytes(out[32 * i: 32 * i + 32].tobytes(), "little") for i in range(n.value)]
+
+
+class PhasedProver:
+    """zk_plonk_prove_phased on the library's key object (keygen.NativeKey): advice in up to three phases with user challenges between them.  `next_phase(phase,
+    challenges, circuit)` is the caller's synthesis of a later phase: it receives the canonical challenge values known so far (0 where not yet squeezed) and returns
+    {column: values} for every column of that phase of that circuit — (n, 4) uint64 Montgomery host arrays, or device buffers when the phase-0 columns are."""
+
+    def __init__(self, params: ParamsKZG, pk: ProvingKey, key=None):
+        from .keygen import NativeKey
+        self.params, self.pk, self.be = params, pk, pk.backend
+        self.key = key if key is not None else NativeKey(params, pk)
+        self.be = self.key.backend
+        self._own_key = key is None
+        cs = pk.vk.cs
+        self.phase_of = cs._advice_phases()
+        self.per_circuit = 32 * (cs.num_advice_columns + 3 * len(cs.lookups) + len(cs.permutation_columns) + len(cs.advice_queries()) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups))
+        self.shared = 32 * (16 + len(cs.fixed_queries()) + 1 + len(cs.permutation_columns) + 8)
+
+    def release(self):
+        if self._own_key:
+            self.key.release()
+
+    def create_proof(self, advices: Sequence[Sequence], instances_list: Sequence[Sequence[Sequence[int]]], rng, next_phase=None, raw_callback=None) -> bytes:
+        """advices[c]: circuit c's advice columns; entries of later-phase columns are ignored (None will do).  raw_callback: a ready PHASE_FN (or None for a NULL
+        callback) instead of the bridge around `next_phase` — tests of the refusals."""
+        be, m, A = self.be, len(advices), self.pk.vk.cs.num_advice_columns
+        n = self.params.n
+        flat = [a for per in advices for a in per]
+        first = [a for i, a in enumerate(flat) if self.phase_of[i % A] == 0]
+        on_device = bool(first) and not isinstance(first[0], np.ndarray)
+        keep, errors = [], []
+
+        def pointer(col):
+            if on_device:
+                keep.append(col)
+                return _dptr(col)
+            a = np.ascontiguousarray(col, dtype=np.uint64).reshape(n, 4)
+            keep.append(a)
+            return a.ctypes.data
+        adv = (C.c_void_p * max(1, len(flat)))(*[pointer(a) if self.phase_of[i % A] == 0 else None for i, a in enumerate(flat)])
+        instances = [col for per in instances_list for col in per]
+        inst = [np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in col) or bytes(32), dtype=np.uint8).copy() for col in instances]
+        inst_ptrs = (C.c_void_p * max(1, len(inst)))(*[a.ctypes.data for a in inst])
+        lens = (C.c_uint32 * max(1, len(inst)))(*[len(col) for col in instances])
+
+        self.draw_counts = counts = []                                   # the sizes of the Fr::random blocks the library asked for, in order (tests of the draw schedule)
+
+        def draw(_user, count, out):
+            try:
+                counts.append(int(count))
+                a = rand_fr_array(rng, int(count))
+                C.memmove(out, a.ctypes.data, a.nbytes)
+            except BaseException as e:                                  # never let an exception cross the FFI
+                errors.append(e)
+
+        def bridge(_user, phase, chal, n_chal, advice_out):             # zk_phase_fn -> next_phase(phase, challenges, circuit)
+            try:
+                from ..fields import fr_int_array
+                ch = fr_int_array(np.ctypeslib.as_array(C.cast(chal, C.POINTER(C.c_uint64)), shape=(n_chal, 4)).copy()) if n_chal else []
+                for c in range(m):
+                    got = next_phase(int(phase), [int(v) for v in ch], c)
+                    for i, col in got.items():
+                        assert self.phase_of[i] == phase, f"column {i} is not in phase {phase}"
+                        advice_out[c * A + i] = pointer(col)
+                return 0
+            except BaseException as e:
+                errors.append(e)
+                return 1
+        cb = RNG_FN(draw)
+        if raw_callback is not None or next_phase is None:
+            phase_cb = raw_callback if raw_callback is not None else C.cast(None, PHASE_FN)
+        else:
+            phase_cb = PHASE_FN(bridge)
+        cap = self.shared + m * self.per_circuit
+        out = np.empty(cap, dtype=np.uint8)
+        ln = C.c_size_t()
+        rc = be.lib.zk_plonk_prove_phased(be.ctx, C.c_uint64(self.key.handle), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, phase_cb, None, cb, None,
+                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
+        if errors:
+            raise errors[0]
+        be._ck(rc)
+        return out[: ln.value].tobytes()
 
 
 class NativeProver:

@@ -14,8 +14,9 @@ Every O(n) step runs on the GPU through the product API and stays resident in HB
     evaluations            zk_eval_polynomial_batch_dev
     SHPLONK                zk_fr_lincomb_dev, zk_kate_division_dev
 The host does what it does in the reference: Fiat-Shamir hashing, point encoding, O(#columns) bookkeeping.
-Single circuit instance per proof (the reference passes `&[circuit]`); no user challenges / multi-phase advice.  This readable twin stays single-circuit:
-one proof over several circuits is the native path's alone (NativeProver.create_proof_multi, zk_plonk_create_proof_multi).
+Single circuit instance per proof (the reference passes `&[circuit]`).  Multi-phase advice and user challenges ([3P-MEM] halo2_proofs v2023_01_20 plonk/prover.rs): the
+advice step runs once per phase and `next_phase` supplies the columns of the later phases from the challenges squeezed so far.  This readable twin stays single-circuit:
+one proof over several circuits is the native path's alone (NativeProver.create_proof_multi, zk_plonk_create_proof_multi, zk_plonk_prove_phased).
 """
 from __future__ import annotations
 
@@ -40,13 +41,17 @@ def rotate_omega(x: int, rot: int, k: int) -> int:
     return x * pow(w, rot % (1 << k), R_MOD) % R_MOD
 
 
-def draw_plan(n_advice: int, n_lookups: int, n_sets: int, n_pieces: int, n: int, bf: int):
+def draw_plan(n_advice: int, n_lookups: int, n_sets: int, n_pieces: int, n: int, bf: int, advice_phase=None):
     """The order in which create_proof consumes the caller's `&mut rng`, as a list of (purpose, index, count of Fr::random draws, squeeze) items; `squeeze` names the
     challenge squeezed AFTER the item's phase (the item is drawn before that squeeze happens in halo2) — tests/test_rust_vectors.py compares the running totals
     with the Rust prover's counting RNG.  This is halo2_proofs v2023_01_20 (PSE; stack A of the reference) draw by draw ([3P-MEM]; include/zkmi355.h zk_rng_fn lists
     the source files): every commitment also draws one Blind(Fr::random) that KZG discards ("blind" items).  csrc/prover.hip builds the same plan (draw_schedule 1)."""
-    plan = [("advice", i, bf + 1, "theta") for i in range(n_advice)]      # rows [usable_rows, n): the bf blinding rows and the one after
-    plan += [("blind", None, 1, "theta")] * n_advice
+    advice_phase = list(advice_phase) if advice_phase is not None else [0] * n_advice
+    plan = []
+    for p in range(max([0] + advice_phase) + 1):                          # phase-major: a phase's rows, then its Blinds (one phase: advice rows, then n_advice Blinds)
+        mine = [i for i in range(n_advice) if advice_phase[i] == p]
+        plan += [("advice", i, bf + 1, "theta") for i in mine]            # rows [usable_rows, n): the bf blinding rows and the one after
+        plan += [("blind", None, 1, "theta")] * len(mine)
     for l in range(n_lookups):
         plan += [("bi", l, bf + 1, "beta"), ("bt", l, bf + 1, "beta"), ("blind", None, 1, "beta"), ("blind", None, 1, "beta")]
     for s in range(n_sets):
@@ -68,22 +73,24 @@ class _Joiner:
 
 
 def create_proof(params: ParamsKZG, pk: ProvingKey, advice: Sequence, instances: Sequence[Sequence[int]], rng: np.random.Generator, transcript,
-                 timings: Optional[dict] = None, capture: Optional[dict] = None, phase_io=None) -> dict:
+                 timings: Optional[dict] = None, capture: Optional[dict] = None, phase_io=None, next_phase=None) -> dict:
     """advice: cs.num_advice_columns columns of n rows — (n, 4) uint64 Montgomery host arrays or device buffers; rows past
     `usable_rows` are overwritten with blinding and device buffers are consumed (they hold coefficients afterwards).  instances:
     canonical ints per instance column.  Writes the proof into `transcript` and returns bookkeeping for tests / benches
     ({"commitments", "evals", "h_eval"}); `timings`, when given, receives wall milliseconds per phase.  Device buffers allocated
     along the way are released (back to the backend's pool) on success and on failure alike.  `capture` (measurement tooling only): receives host
-    copies of the proof's committed Lagrange columns and challenges, so that a driver of the per-call host-buffer entry points can replay them."""
+    copies of the proof's committed Lagrange columns and challenges, so that a driver of the per-call host-buffer entry points can replay them.
+    next_phase(phase, challenges) -> {column: values}: the caller's synthesis of advice phase 1, 2 from the canonical challenge values squeezed so far (0 where not yet
+    squeezed); the entries of later-phase columns in `advice` are ignored."""
     owned: List = []
     try:
-        return _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture, phase_io)
+        return _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture, phase_io, next_phase)
     finally:
         for d in owned:
             d.free()
 
 
-def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture=None, phase_io=None) -> dict:
+def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture=None, phase_io=None, next_phase=None) -> dict:
     be, cs, k, n = pk.backend, pk.vk.cs, params.k, params.n
     dom = pk.domain
     ek, en = dom.extended_k, dom.extended_n
@@ -137,19 +144,21 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
     # ---- 2. advice: blind the unusable rows, commit ----------------------------------------------------------------------
     # host columns (what halo2's prover holds after synthesis: Vec<Fr> per column) cross PCIe here, all in one call; page-locked arrays
     # (Backend.host_alloc) travel at link rate.  Device buffers are taken as they are.
-    adv_values = [dev(n * 32) if isinstance(col, np.ndarray) else col for col in advice]
-    from_host = [i for i, col in enumerate(advice) if isinstance(col, np.ndarray)]
-    if from_host:
-        be.upload_columns([adv_values[i] for i in from_host], [np.ascontiguousarray(advice[i], dtype=np.uint64).reshape(n, 4) for i in from_host], n * 32)
+    phase_of = cs._advice_phases()
+    n_phases = len(cs.phases())
+    assert n_phases == 1 or next_phase is not None, "a circuit with advice in later phases needs next_phase"
+    A = len(advice)
     # Every `Fr::random` draw of the proof (blinding rows, the n coefficients of the vanishing argument's random polynomial, the Blind every commitment
-    # draws and KZG discards) depends on no challenge: the advice rows are drawn here, a helper thread draws the rest, in draw_plan's order (the stream —
-    # hence the proof — is the same), while the GPU commits the advice columns; a phase waits only for its own items.
+    # draws and KZG discards) depends on no challenge: the advice section (every phase's rows and Blinds) is drawn here, a helper thread draws the rest, in
+    # draw_plan's order (the stream — hence the proof — is the same), while the GPU commits the advice columns; a phase waits only for its own items.
     chunk = cs.permutation_chunk_len()
     n_sets = (len(cs.permutation_columns) + chunk - 1) // chunk if cs.permutation_columns else 0
-    plan = draw_plan(len(advice), L, n_sets, dom.quotient_poly_degree, n, bf)
-    blinds = [rand_fr_array(rng, cnt) for _, _, cnt, _ in plan[:len(advice)]]
-    if advice:
-        be.upload_columns([d.ptr + usable * 32 for d in adv_values], blinds, (n - usable) * 32)
+    plan = draw_plan(A, L, n_sets, dom.quotient_poly_degree, n, bf, advice_phase=phase_of)
+    blinds = {}
+    for name, idx, cnt, _ in plan[:2 * A]:
+        a_ = rand_fr_array(rng, cnt)
+        if name == "advice":
+            blinds[idx] = a_
     drawn = {name: {} for name in ("bi", "bt", "perm_blind", "lookup_blind", "random_poly")}
     ready = {name: threading.Event() for name in drawn}
     want = {name: sum(1 for it_ in plan if it_[0] == name) for name in drawn}
@@ -160,7 +169,7 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
 
     def draw_all():
         try:
-            for name, idx, cnt, _ in plan[len(advice):]:
+            for name, idx, cnt, _ in plan[2 * A:]:
                 a = rand_fr_array(rng, cnt)
                 if name == "blind":
                     continue
@@ -186,8 +195,29 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
     drawer = threading.Thread(target=draw_all)
     drawer.start()
     owned.append(_Joiner(drawer))                                    # joined on every exit path (the generator belongs to the caller again afterwards)
-    for pt in commit_all("g_lagrange", adv_values):
-        transcript.write_point(pt)
+    # per phase: the caller's columns of that phase (phase 0: `advice`), blinded, committed in ascending index; then the phase's challenges in ascending index
+    adv_values = [None] * A
+    cols_in = list(advice)
+    challenges = [0] * cs.num_challenges
+    for p in range(n_phases):
+        mine = [i for i in range(A) if phase_of[i] == p]
+        if p:
+            got = next_phase(p, list(challenges))
+            for i in mine:
+                cols_in[i] = got[i]
+        for i in mine:
+            adv_values[i] = dev(n * 32) if isinstance(cols_in[i], np.ndarray) else cols_in[i]
+        from_host = [i for i in mine if isinstance(cols_in[i], np.ndarray)]
+        if from_host:
+            be.upload_columns([adv_values[i] for i in from_host], [np.ascontiguousarray(cols_in[i], dtype=np.uint64).reshape(n, 4) for i in from_host], n * 32)
+        if mine:
+            be.upload_columns([adv_values[i].ptr + usable * 32 for i in mine], [blinds[i] for i in mine], (n - usable) * 32)
+        for pt in commit_all("g_lagrange", [adv_values[i] for i in mine]):
+            transcript.write_point(pt)
+        for ci, cp in enumerate(cs.challenge_phase):
+            if cp == p:
+                challenges[ci] = transcript.squeeze_challenge()
+    ch_m = [fr_mont(c) for c in challenges]
 
     lap("2_advice_commit")
     # ---- 3. theta; lookups: compress, permute, commit --------------------------------------------------------------------
@@ -202,7 +232,7 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
     def run_compressor(evl):
         out = dev(n * 32)
         evl.evaluate_h(fixed=pk.fixed_values, advice=adv_values, instance=inst_values, l0=anycol, l_last=anycol, l_active_row=anycol,
-                       perm_cosets=[], perm_products=[], lookup_product=[], lookup_input=[], lookup_table=[], challenges=[],
+                       perm_cosets=[], perm_products=[], lookup_product=[], lookup_input=[], lookup_table=[], challenges=ch_m,
                        beta=one, gamma=one, theta=th, y=one, out=out)
         return out
     for lk, (cin_ev, ctab_ev) in zip(cs.lookups, pk.lookup_compressors):
@@ -262,7 +292,7 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
     def split(ext):
         return dict(advice=ext[:nA], instance=ext[nA:nA + nI], perm_products=ext[nA + nI:nA + nI + nZ], lookup_product=ext[nA + nI + nZ:nA + nI + nZ + L],
                     lookup_input=ext[nA + nI + nZ + L:][0::2], lookup_table=ext[nA + nI + nZ + L:][1::2])
-    scal = dict(challenges=[], beta=bt_m, gamma=gm_m, theta=th, y=fr_mont(y))
+    scal = dict(challenges=ch_m, beta=bt_m, gamma=gm_m, theta=th, y=fr_mont(y))
     n_pieces = dom.quotient_poly_degree
     h_ext = dev(en * 32) if not pk.pieces_from_cosets else None
     numer = []
