@@ -68,8 +68,8 @@ def ladder_program(slots, k):
 
 def launch_shape(slots, rows, threads):
     """quotient_run's choice for a program of `slots` slots on `rows` rows under tune quot_threads = `threads`: (T, dynamic LDS bytes).  A restatement of
-    csrc/quotient.hip (quotient_run: from `uint32_t T = (uint32_t)std::min(ctx->tune.quot_threads, 256)` to `const size_t lds`; DESIGN.md 3.3), so that a test can say which
-    rung it stands on — it reads nothing from the library; slot 0 is a register"""
+    quot_launch_shape (csrc/quotient.hip; DESIGN.md 3.3), so that a test can say which rung it stands on without a library at hand;
+    test_structured_programs.test_launch_shape_of_every_rung pins it against that function.  Slot 0 is a register"""
     T = min(threads, 256, rows)
     while T > 64 and (slots - 1) * T * 32 > 32 * 1024:
         T >>= 1

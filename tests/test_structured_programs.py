@@ -7,6 +7,7 @@ three or four slots (live intermediates), which is ONE launch shape of the inter
 
 Every case goes through quotient_cases.run_case: whole domain, first and last coset, coset parts, four row slices per coset and the two degree parts, each bit for bit
 against the oracle (oracle/evaluate_h_oracle.inc).  CPU: the kernel emulator.  GPU: the product library, on the interpreter and on the generated kernels."""
+import ctypes as C
 import re
 import time
 
@@ -68,17 +69,28 @@ def test_emulated_slot_ladder(emu, orc, pyref, slots):
     qc.run_case(emu, orc, pyref, pc, prog, seed=slots)
 
 
-def test_launch_shape_of_every_rung():
-    """This pins program_cases.launch_shape, a RESTATEMENT in Python of quotient_run's choice (csrc/quotient.hip, from `uint32_t T = (uint32_t)std::min(ctx->tune.quot_threads,
-    256)` down to `const size_t lds = ...`), not the library: nothing in the C ABI reports the threads or the LDS bytes of a launch.  What it shows is that the ladder's slot
-    counts stand on either side of every threshold of that formula; whoever changes the T loop in quotient.hip changes launch_shape with it and re-reads this table.  The GPU
-    cases quote these figures in their messages, they do not measure them (a kernel trace of the ladder shows the workgroup sizes: DESIGN.md 3.3)."""
+def _library_shape(be, slots, rows, threads):
+    """quot_launch_shape / quot_slots_fit of the emulator build (csrc/quotient.hip, through the test-only export): ((T, LDS bytes), a program of that many slots is loaded)"""
+    t, lds = C.c_uint32(), C.c_size_t()
+    fits = be.lib.zk_test_quot_launch_shape(C.c_uint32(slots), C.c_int(threads), C.c_uint64(rows), C.byref(t), C.byref(lds))
+    return (t.value, lds.value), bool(fits)
+
+
+def test_launch_shape_of_every_rung(emu):
+    """program_cases.launch_shape is a restatement in Python of quot_launch_shape (csrc/quotient.hip), the one function quotient_run takes the threads and the LDS bytes
+    of every launch from; it is pinned here against that function (zk_test_quot_launch_shape of the emulator build) and against the literal table below.  What the table
+    shows is that the ladder's slot counts stand on either side of every threshold of the rule.  The GPU cases quote these figures in their messages, they do not measure
+    them (a kernel trace of the ladder shows the workgroup sizes: DESIGN.md 3.3)."""
     shapes = {s: pg.launch_shape(s, 256, 256) for s in LADDER}
     assert shapes == {5: (256, 32768), 6: (128, 20480), 9: (128, 32768), 10: (64, 18432), 33: (64, 65536), 34: (64, 67584), 81: (64, 163840)}
     # under the default quot_threads = 128 the first three rungs share 128 threads
     assert [pg.launch_shape(s, 256, 128)[0] for s in LADDER] == [128, 128, 128, 64, 64, 64, 64]
     # 16 rows per coset, row slices of 4: clipped to the row count
     assert pg.launch_shape(34, 4, 128) == (4, 33 * 4 * 32)
+    # the library's own function: every rung at both thread settings, the clipped case, slots 1 and 2 (no LDS / the first LDS slot) and the slot that is refused
+    for slots, rows, threads in [(s, 256, t) for s in LADDER for t in (256, 128)] + [(34, 4, 128)] + [(s, 256, t) for s in (1, 2, pg.MAX_SLOTS + 1) for t in (256, 128)]:
+        assert _library_shape(emu, slots, rows, threads) == (pg.launch_shape(slots, rows, threads), slots <= pg.MAX_SLOTS), (slots, rows, threads)
+    assert _library_shape(emu, 1, 256, 256)[0] == (256, 0) and _library_shape(emu, 2, 256, 256)[0] == (256, 256 * 32)
 
 
 def test_emulated_one_slot_too_many_is_refused(emu, orc, pyref):

@@ -3,7 +3,7 @@
 #include <string.h>
 #include <new>
 #include <system_error>
-#include "ctx.h"
+#include "quotient.h"
 
 namespace zk {
 int ntt_set_lds_attr();
@@ -47,9 +47,6 @@ int quotient_program_release(zk_ctx* ctx, uint64_t prog);
 int quotient_program_info(zk_ctx* ctx, uint64_t prog, uint32_t* n_instr, uint32_t* n_slots, uint32_t* n_columns);
 int quotient_program_kernels(zk_ctx* ctx, uint64_t prog, uint32_t* n_kernels);
 int quotient_program_opmix(zk_ctx* ctx, uint64_t prog, uint32_t part, uint32_t counts[9]);
-struct QuotRowList;
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
-                 const QuotRowList* rl = nullptr);
 int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written, const void* challenges = nullptr,
                        uint32_t n_challenges = 0, bool phased = false);
 int quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low);
@@ -544,43 +541,57 @@ int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const vo
     if (n_challenges > ZK_MAX_CHALLENGES) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_verify_phased: %u challenges, the quotient interpreter's constant bank is sized for %u", n_challenges, ZK_MAX_CHALLENGES);
     return mock_prover_verify(ctx, desc, out, cap, counts, n_written, challenges, n_challenges, true);
 } ZK_ABI_CATCH(ctx)
-int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 0, 0, 0); } ZK_ABI_CATCH(ctx)
+int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, QuotRoute{}); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset) ZK_ABI_TRY {
     ENTER;
     ARGS_SIZE("zk_quotient_run_coset_dev");
     if (coset >= (1u << 16)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_dev: coset %u out of range", coset);
-    return quotient_run(ctx, prog, args, (int)coset, 0, 0, 0, 0, 0);
+    QuotRoute r;
+    r.coset = (int)coset;
+    return quotient_run(ctx, prog, args, r);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_rows_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint64_t row_lo, uint64_t row_count) ZK_ABI_TRY {
     ENTER;
     ARGS_SIZE("zk_quotient_run_coset_rows_dev");
     if (coset >= (1u << 16)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_rows_dev: coset %u out of range", coset);
     if (!row_count) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_rows_dev: row_count = 0");
-    return quotient_run(ctx, prog, args, (int)coset, row_lo, row_count, 0, 0, 0);
+    QuotRoute r;
+    r.coset = (int)coset; r.row_lo = row_lo; r.row_count = row_count;
+    return quotient_run(ctx, prog, args, r);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low) ZK_ABI_TRY { ENTER; return quotient_program_split(ctx, prog, low_cosets, n_instr_high, n_instr_low); } ZK_ABI_CATCH(ctx)
-int zk_quotient_run_high_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_high_dev"); return quotient_run(ctx, prog, args, -1, 0, 0, 1, 0, 0); } ZK_ABI_CATCH(ctx)
+int zk_quotient_run_high_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY {
+    ENTER; ARGS_SIZE("zk_quotient_run_high_dev");
+    QuotRoute r;
+    r.part = 1;
+    return quotient_run(ctx, prog, args, r);
+} ZK_ABI_CATCH(ctx)
 int zk_quotient_run_low_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t low_cosets) ZK_ABI_TRY {
     ENTER; ARGS_SIZE("zk_quotient_run_low_dev");
     if (!low_cosets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_low_dev: low_cosets = 0");
-    return quotient_run(ctx, prog, args, -1, 0, 0, 2, low_cosets, 0);
+    QuotRoute r;
+    r.part = 2; r.low_cosets = low_cosets;
+    return quotient_run(ctx, prog, args, r);
 } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_part_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part) ZK_ABI_TRY {
     ENTER; ARGS_SIZE("zk_quotient_run_coset_part_dev");
     if (coset >= (1u << 16) || part < 1 || part > 2) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_part_dev: coset %u / part %u out of range", coset, part);
-    return quotient_run(ctx, prog, args, (int)coset, 0, 0, (int)part, 0, 0);
+    QuotRoute r;
+    r.coset = (int)coset; r.part = (int)part;
+    return quotient_run(ctx, prog, args, r);
 } ZK_ABI_CATCH(ctx)
 // halo2's fold across the circuits of one proof: out <- out * y^E + numerator (coset = UINT32_MAX: the whole extended domain; part 2 there: the program's low cosets)
 int zk_quotient_run_acc_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset, uint32_t part) ZK_ABI_TRY {
     ENTER; ARGS_SIZE("zk_quotient_run_acc_dev");
     if ((coset != UINT32_MAX && coset >= (1u << 16)) || part > 2) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_acc_dev: coset %u / part %u out of range", coset, part);
-    uint32_t low_cosets = 0;
+    QuotRoute r;
+    r.coset = coset == UINT32_MAX ? -1 : (int)coset; r.part = (int)part; r.accumulate = true;
     if (coset == UINT32_MAX && part == 2) {
-        int rc = quotient_program_split(ctx, prog, &low_cosets, nullptr, nullptr);
+        int rc = quotient_program_split(ctx, prog, &r.low_cosets, nullptr, nullptr);
         if (rc) return rc;
-        if (!low_cosets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_acc_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
+        if (!r.low_cosets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_acc_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
     }
-    return quotient_run(ctx, prog, args, coset == UINT32_MAX ? -1 : (int)coset, 0, 0, (int)part, low_cosets, 1);
+    return quotient_run(ctx, prog, args, r);
 } ZK_ABI_CATCH(ctx)
 
 int zk_pk_load(zk_ctx* ctx, uint64_t prog, const void* const* fixed, const void* const* sigma, const void* l0, const void* l_last, const void* l_active,

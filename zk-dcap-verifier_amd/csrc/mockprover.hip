@@ -381,7 +381,7 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
         {
             MpTimer t(ctx, "mock_gates");
             qa.out = work;
-            rc = quotient_run(ctx, progs.h.back(), &qa, -1, 0, 0, 0, 0, 0);
+            rc = quotient_run(ctx, progs.h.back(), &qa, QuotRoute{});
             if (rc) return rc;
             uint8_t* flags = (uint8_t*)mem.get(u);
             if (!flags) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
@@ -396,7 +396,9 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
             uint32_t* d_bits = (uint32_t*)mem.get((size_t)n_rows * words * 4);
             if (!d_bits) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_verify: device allocation failed");
             const QuotRowList rl{list, n_rows, d_bits, words};
-            rc = quotient_run(ctx, progs.h.back(), &qa, -1, 0, 0, 0, 0, 0, &rl);
+            QuotRoute route;
+            route.rows = &rl;
+            rc = quotient_run(ctx, progs.h.back(), &qa, route);
             if (rc) return rc;
             rows.resize(n_rows);
             bits.resize((size_t)n_rows * words);
@@ -420,7 +422,7 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
             if (rc_) return rc_;
             progs.h.push_back(p);
             qa.out = dst;
-            rc_ = quotient_run(ctx, p, &qa, -1, 0, 0, 0, 0, 0);
+            rc_ = quotient_run(ctx, p, &qa, QuotRoute{});
             progs.h.back() = 0;
             (void)quotient_program_release(ctx, p);
             return rc_;

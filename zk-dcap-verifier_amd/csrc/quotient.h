@@ -4,8 +4,10 @@
 #include "ctx.h"
 
 namespace zk {
-// micro-ops
-enum { M_ADD = 0, M_SUB, M_MUL, M_SQR, M_DBL, M_NEG, M_MOV, M_MULADD, M_FOLD2 };   // M_FOLD2: acc = acc * c + a * b with ONE Montgomery reduction (value = value * y + product)
+// micro-ops, in opcode order (what each one computes: quot_exec.inc, QOP_<name>).  M_FOLD2: acc = acc * c + a * b with ONE Montgomery reduction (value = value * y + product)
+#define QUOT_OPS(X) X(ADD) X(SUB) X(MUL) X(SQR) X(DBL) X(NEG) X(MOV) X(MULADD) X(FOLD2)
+#define QUOT_OP_ENUM(name) M_##name,
+enum { QUOT_OPS(QUOT_OP_ENUM) M_COUNT };
 enum { K_SLOT = 0, K_CONST, K_COL, K_ACC, K_XPOW, K_NONE = 7 };
 
 struct QuotProgram {
@@ -51,12 +53,37 @@ bool quot_jit_ready(const QuotProgram& P);
 uint32_t quot_jit_kernel_count(const QuotProgram& P);
 int quot_jit_launch(zk_ctx* ctx, const QuotProgram& P, const QuotArgs& q, uint64_t rows, uint32_t threads);
 
+// The launch shape of a program of n_slots slots (quotient.hip): slot 0 is a register, the others take 32 bytes of LDS per thread; a workgroup has min(tune quot_threads,
+// 256, rows) threads, halved down to 64 while its slots exceed 32 KiB; a program fits when 64 threads' slots fit the 160 KiB of a CU.
+struct QuotShape { uint32_t threads; size_t lds_bytes; };
+uint32_t quot_lds_slots(uint32_t n_slots);
+bool quot_slots_fit(uint32_t n_slots);
+QuotShape quot_launch_shape(uint32_t n_slots, int quot_threads, uint64_t rows);
+
 // Row-list mode of quotient_run (mockprover.hip, gate attribution): the program runs on rows[0 .. n) of its domain only, and instead of the value every thread
 // writes one bit per fold of the accumulator: bit f of bits[i * words + f / 32] = the f-th folded term of row rows[i] is non-zero after full reduction.  For the
 // program of quotient_program_load_gates the folds are exactly the gate polynomials, in cs.gates order.
 struct QuotRowList { const uint32_t* rows; uint32_t n; uint32_t* bits; uint32_t words; };
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
-                 const QuotRowList* rl = nullptr);
+// Which rows of which program a run evaluates; the defaults are the whole extended domain and every identity.
+// coset = j >= 0: only coset j of the extended domain — the rows j, j + 2^(ek-k), ... — with columns given as that coset's n = 2^k values (zk_coeff_to_coset_batch_dev);
+// rotations then step by one row.  The 2^(ek-k) cosets are independent, which is what lets a proof's quotient be split over GPUs: out receives the n
+// numerator values of the coset.
+// row_count > 0: only rows [row_lo, row_lo + row_count) of that domain (the columns are complete, so rotations need no halo), out[i] = row row_lo + i — the unit that
+// lets more ranks than cosets share a quotient.
+// part: 0 = every identity; 1 / 2 = the high / low part of a program that has a degree split (QuotProgram::part_hi / part_lo).  low_cosets > 0 (part 2, coset < 0): the
+// columns are the whole extended domain but only the rows of its cosets 0 .. low_cosets-1 are evaluated — thread i of coset j reads row i * 2^(ek-k) + j — and out
+// receives low_cosets x n values, coset-major (what zk_cosets_to_pieces_dev takes).
+// accumulate: out holds halo2's PreviousValue and receives out * y^E + numerator (quot_args.inc).  rows: row-list mode — a program of extended_k = k that does not
+// read X, on the whole domain.
+struct QuotRoute {
+    int coset = -1;
+    uint64_t row_lo = 0, row_count = 0;
+    int part = 0;
+    uint32_t low_cosets = 0;
+    bool accumulate = false;
+    const QuotRowList* rows = nullptr;
+};
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, const QuotRoute& route);
 // The custom gates of an Evaluator blob (ZKQ1) alone, compiled at extended_k = k: value(row) = sum_i y^(E-1-i) gate_i(row), rotations mod 2^k (the permutation and
 // the lookups of the blob are dropped).  *n_polys = E, the parts of the blob's final Horner(previous, gates, y); E = 0 loads nothing (*prog = 0).
 int quotient_program_load_gates(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog, uint32_t* n_polys);

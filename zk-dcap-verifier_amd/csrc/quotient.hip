@@ -36,8 +36,7 @@ enum { OP_ADD = 0, OP_SUB, OP_MUL, OP_SQUARE, OP_DOUBLE, OP_NEGATE, OP_HORNER, O
 #define ZK_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
 #endif
 
-constexpr uint32_t QUOT_NREG = 1;   // first slot of the allocator is a register, the rest LDS (3 -> 1: 128 -> 116 VGPRs, 9.74 -> 9.18 ms at k = 19: profiles/r02)
-
+#include "quot_exec.inc"   // the micro-ops, the row mapping, the X power, the epilogue and the LDS slot layout: shared with the generated kernels
 
 // One row per thread.  The loop is software-pipelined by one instruction: while instruction pc executes, the column /
 // constant operands of instruction pc + 1 are already in flight (the kernel is otherwise bound by the latency of ~850
@@ -46,41 +45,21 @@ constexpr uint32_t QUOT_NREG = 1;   // first slot of the allocator is a register
 ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) ZK_WAVES_PER_EU(4) quotient_kernel(QuotArgs q) {
     ZK_DYN_SHARED(uint4, smem);
     const uint32_t T = blockDim.x, tid = threadIdx.x;
-    uint32_t idx0 = q.row_base + blockIdx.x * T + tid;                // this thread's row
-    uint32_t oidx = idx0 - q.row_base;
-    if (q.strided) {
-        const uint32_t j = idx0 & ((1u << q.sub_log) - 1u), i = idx0 >> q.sub_log;
-        idx0 = (i << q.stride_log) + j;
-        oidx = (j << q.k_log) + i;
-    }
+    uint32_t idx0, oidx;                                              // this thread's row and where its value goes
+    quot_row(q, blockIdx.x * T + tid, idx0, oidx);
     const uint32_t mask = (1u << q.size_log) - 1u;
     u256 acc = Fr::zero(), xpow = Fr::one(), rg0 = Fr::zero();        // slot 0 lives in VGPRs
-    if (q.uses_xpow) {  // extended_omega^(position of this row in the extended domain)
-        const uint32_t xi = idx0 * q.xpow_mul + q.xpow_add;
-        xpow = load_u256(q.tw_lo, xi & ((1u << q.lo_bits) - 1u));
-        const uint32_t h = xi >> q.lo_bits;
-        if (h) xpow = Fr::mul(xpow, load_u256(q.tw_hi, h));
-    }
+    if (q.uses_xpow) xpow = quot_xpow(q, idx0);
     auto prefetch = [&](uint32_t src) -> u256 {        // memory operands only; everything else is resolved later
         const uint32_t kind = src >> 28, pay = src & 0x0fffffffu;
-        if (kind == K_COL) return load_u256(q.cols[pay >> 8], (idx0 + q.rot_off[pay & 0xffu]) & mask);
-        if (kind == K_CONST) return load_u256(q.consts, pay);
+        if (kind == K_COL) return LDCOL(pay >> 8, pay & 0xffu);
+        if (kind == K_CONST) return LDC(pay);
         return Fr::zero();
     };
     auto resolve = [&](uint32_t src, const u256& pre) -> u256 {
         const uint32_t kind = src >> 28, pay = src & 0x0fffffffu;
         switch (kind) {
-            case K_SLOT: {
-                switch (pay) {
-                    case 0: return rg0;
-                    default: break;
-                }
-                const uint32_t ls = pay - QUOT_NREG;
-                uint4 l = smem[(2 * ls) * T + tid], h = smem[(2 * ls + 1) * T + tid];
-                u256 o;
-                o.v[0] = l.x; o.v[1] = l.y; o.v[2] = l.z; o.v[3] = l.w; o.v[4] = h.x; o.v[5] = h.y; o.v[6] = h.z; o.v[7] = h.w;
-                return o;
-            }
+            case K_SLOT: return pay < QUOT_NREG ? rg0 : quot_slot_load(smem, pay - QUOT_NREG, T, tid);
             case K_ACC: return acc;
             case K_XPOW: return xpow;
             default: return pre;       // K_COL / K_CONST (already loaded) or K_NONE
@@ -97,39 +76,15 @@ ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) ZK_WAVES_PER_EU(4) quotient_kernel(QuotArgs
             nxt = q.code[pc + 1];
             na = prefetch(ZK_UNIFORM(nxt.y)); nb = prefetch(ZK_UNIFORM(nxt.z)); nc = prefetch(ZK_UNIFORM(nxt.w));
         }
-        const uint32_t op = w0 & 0xffu;
-        u256 res;
         const u256 a = resolve(sa, pa);
-        switch (op) {
-            // every value of a row (slots, accumulator) lives in [0, 2p] (field.cuh, redundant ranges): products skip their final subtraction, sums and
-            // differences are corrected by 2p (same cost as by p), memory operands arrive canonical, and the row's result is normalised once at the end
-            case M_ADD: res = Fr::red2p(Fr::add_lazy(a, resolve(sb, pb))); break;
-            case M_SUB: res = Fr::sub2(a, resolve(sb, pb)); break;
-            case M_MUL: res = Fr::mul_lazy(a, resolve(sb, pb)); break;
-            case M_SQR: res = Fr::sqr_lazy(a); break;
-            case M_DBL: res = Fr::dbl2(a); break;
-            case M_NEG: res = Fr::neg2(a); break;
-            case M_MULADD: res = Fr::red2p(Fr::add_lazy(Fr::mul_lazy(a, resolve(sb, pb)), resolve(sc, pc_))); break;
-            case M_FOLD2: res = Fr::mul2_add_2p(acc, resolve(sc, pc_), a, resolve(sb, pb)); break;
-            default: res = a; break;
-        }
-        if ((w0 >> 8) & 0xffu) {
-            acc = res;
-        } else {
-            const uint32_t slot = w0 >> 16;
-            switch (slot) {
-                case 0: rg0 = res; break;
-                default: {
-                    const uint32_t ls = slot - QUOT_NREG;
-                    smem[(2 * ls) * T + tid] = make_uint4(res.v[0], res.v[1], res.v[2], res.v[3]);
-                    smem[(2 * ls + 1) * T + tid] = make_uint4(res.v[4], res.v[5], res.v[6], res.v[7]);
-                }
-            }
-        }
+        u256 res;
+        QOP_SWITCH(w0 & 0xffu, res, a, resolve(sb, pb), resolve(sc, pc_), acc);
+        if ((w0 >> 8) & 0xffu) acc = res;
+        else if ((w0 >> 16) < QUOT_NREG) rg0 = res;
+        else quot_slot_store(smem, (w0 >> 16) - QUOT_NREG, T, tid, res);
         ins = nxt; pa = na; pb = nb; pc_ = nc;
     }
-    if (q.accumulate) acc = Fr::red2p(Fr::add_lazy(Fr::mul_lazy(load_u256(q.out, oidx), load_u256(q.consts, q.acc_const)), acc));      // previous * y^E + this numerator
-    store_u256(q.out, oidx, Fr::normalize(acc));
+    quot_finish(q, oidx, acc);
 }
 
 // A micro-op that folds one identity into the accumulator: acc = acc * y^e + term (M_MULADD with the accumulator as first operand and destination), or
@@ -151,17 +106,10 @@ ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) quotient_rows_kernel(QuotArgs q, const uint
     auto rd = [&](uint32_t src) -> u256 {
         const uint32_t kind = src >> 28, pay = src & 0x0fffffffu;
         switch (kind) {
-            case K_COL: return load_u256(q.cols[pay >> 8], (idx0 + q.rot_off[pay & 0xffu]) & mask);
-            case K_CONST: return load_u256(q.consts, pay);
+            case K_COL: return LDCOL(pay >> 8, pay & 0xffu);
+            case K_CONST: return LDC(pay);
             case K_ACC: return acc;
-            case K_SLOT: {
-                if (pay < QUOT_NREG) return rg0;
-                const uint32_t ls = pay - QUOT_NREG;
-                const uint4 l = smem[(2 * ls) * T + tid], h = smem[(2 * ls + 1) * T + tid];
-                u256 o;
-                o.v[0] = l.x; o.v[1] = l.y; o.v[2] = l.z; o.v[3] = l.w; o.v[4] = h.x; o.v[5] = h.y; o.v[6] = h.z; o.v[7] = h.w;
-                return o;
-            }
+            case K_SLOT: return pay < QUOT_NREG ? rg0 : quot_slot_load(smem, pay - QUOT_NREG, T, tid);
             default: return Fr::zero();
         }
     };
@@ -171,35 +119,16 @@ ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) quotient_rows_kernel(QuotArgs q, const uint
         const uint32_t w0 = ZK_UNIFORM(ins.x), sa = ZK_UNIFORM(ins.y), sb = ZK_UNIFORM(ins.z), sc = ZK_UNIFORM(ins.w), op = w0 & 0xffu;
         const u256 a = rd(sa);
         u256 res;
-        switch (op) {
-            case M_ADD: res = Fr::red2p(Fr::add_lazy(a, rd(sb))); break;
-            case M_SUB: res = Fr::sub2(a, rd(sb)); break;
-            case M_MUL: res = Fr::mul_lazy(a, rd(sb)); break;
-            case M_SQR: res = Fr::sqr_lazy(a); break;
-            case M_DBL: res = Fr::dbl2(a); break;
-            case M_NEG: res = Fr::neg2(a); break;
-            case M_MULADD: res = Fr::red2p(Fr::add_lazy(Fr::mul_lazy(a, rd(sb)), rd(sc))); break;
-            case M_FOLD2: res = Fr::mul2_add_2p(acc, rd(sc), a, rd(sb)); break;
-            default: res = a; break;
-        }
+        QOP_SWITCH(op, res, a, rd(sb), rd(sc), acc);
         if (quot_is_fold(w0, sa)) {
             const u256 term = op == M_FOLD2 ? Fr::mul_lazy(a, rd(sb)) : rd(sc);
             if (!Fr::is_zero(Fr::normalize(term))) word |= 1u << (fold & 31u);
             if ((fold & 31u) == 31u && fold / 32 < words) { bits[(size_t)i * words + fold / 32] = word; word = 0; }
             fold++;
         }
-        if ((w0 >> 8) & 0xffu) {
-            acc = res;
-        } else {
-            const uint32_t slot = w0 >> 16;
-            if (slot < QUOT_NREG) {
-                rg0 = res;
-            } else {
-                const uint32_t ls = slot - QUOT_NREG;
-                smem[(2 * ls) * T + tid] = make_uint4(res.v[0], res.v[1], res.v[2], res.v[3]);
-                smem[(2 * ls + 1) * T + tid] = make_uint4(res.v[4], res.v[5], res.v[6], res.v[7]);
-            }
-        }
+        if ((w0 >> 8) & 0xffu) acc = res;
+        else if ((w0 >> 16) < QUOT_NREG) rg0 = res;
+        else quot_slot_store(smem, (w0 >> 16) - QUOT_NREG, T, tid, res);
     }
     if ((fold & 31u) && fold / 32 < words) bits[(size_t)i * words + fold / 32] = word;
 }
@@ -860,6 +789,28 @@ static int compile_program(zk_ctx* ctx, const uint32_t* words, size_t nwords, Qu
     return ZK_OK;
 }
 
+// ---- launch shape (quotient.h) ------------------------------------------------------------------
+constexpr size_t QUOT_LDS_MAX = 160 * 1024;      // the LDS of a CU: what one workgroup of the interpreter may ask for
+uint32_t quot_lds_slots(uint32_t n_slots) { return n_slots > QUOT_NREG ? n_slots - QUOT_NREG : 0; }
+bool quot_slots_fit(uint32_t n_slots) { return (size_t)quot_lds_slots(n_slots) * 64 * 32 <= QUOT_LDS_MAX; }
+QuotShape quot_launch_shape(uint32_t n_slots, int quot_threads, uint64_t rows) {
+    uint32_t T = (uint32_t)std::min(quot_threads, 256);               // the kernels are compiled for <= 256 threads per workgroup
+    if (T > rows) T = (uint32_t)rows;
+    const uint32_t lds_slots = quot_lds_slots(n_slots);
+    while (T > 64 && (size_t)lds_slots * T * 32 > 32 * 1024) T >>= 1;
+    if (T < 1) T = 1;
+    return QuotShape{T, (size_t)lds_slots * T * 32};
+}
+static int slots_refused(zk_ctx* ctx, const QuotProgram& P) {
+    return ctx->fail(ZK_ERR_LIMIT, "quotient program needs %u live intermediates; this build keeps at most %zu (one in a register, the others in LDS)", P.n_slots,
+                     QUOT_NREG + QUOT_LDS_MAX / (64 * 32));
+}
+static bool upload_code(QuotProgram& Q) {
+    hipError_t e = hipMalloc(&Q.d_code, Q.code.size() * 16 + 16);
+    if (e == hipSuccess) e = hipMemcpy(Q.d_code, Q.code.data(), Q.code.size() * 16, hipMemcpyHostToDevice);
+    return e == hipSuccess;
+}
+
 int quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog) {
     if (!blob || !prog || len < 48 || (len & 3)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_program_load: bad blob pointer/length");
     std::vector<uint32_t> words(len / 4);
@@ -868,14 +819,8 @@ int quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* p
     P->device = ctx->device;
     int rc = compile_program(ctx, words.data(), words.size(), *P);
     if (rc) return rc;
-    if ((size_t)(P->n_slots > QUOT_NREG ? P->n_slots - QUOT_NREG : 0) * 64 * 32 > 160 * 1024)
-        return ctx->fail(ZK_ERR_LIMIT, "quotient program needs %u live intermediates; this build keeps at most 80 in LDS", P->n_slots);
-    auto upload = [&](QuotProgram& Q) -> bool {
-        hipError_t e = hipMalloc(&Q.d_code, Q.code.size() * 16 + 16);
-        if (e == hipSuccess) e = hipMemcpy(Q.d_code, Q.code.data(), Q.code.size() * 16, hipMemcpyHostToDevice);
-        return e == hipSuccess;
-    };
-    if (!upload(*P)) return ctx->fail(ZK_ERR_HIP, "zk_quotient_program_load: device allocation failed");
+    if (!quot_slots_fit(P->n_slots)) return slots_refused(ctx, *P);
+    if (!upload_code(*P)) return ctx->fail(ZK_ERR_HIP, "zk_quotient_program_load: device allocation failed");
     // the same program by degree (QuotProgram::part_hi / part_lo): worth it when the extended domain has at least four cosets' worth of rows per low-part coset pair,
     // i.e. cs_degree >= 4, and both parts hold identities
     if (ctx->tune.quot_degree_split && P->degree > SPLIT_LOW_DEGREE && P->ek > P->k) {
@@ -883,7 +828,7 @@ int quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* p
         hi->device = lo->device = ctx->device;
         if (compile_program(ctx, words.data(), words.size(), *hi, 1) == ZK_OK && compile_program(ctx, words.data(), words.size(), *lo, 2) == ZK_OK &&
             hi->folds_taken && lo->folds_taken && hi->n_slots <= P->n_slots + 8 && lo->n_slots <= P->n_slots + 8) {
-            if (!upload(*hi) || !upload(*lo)) return ctx->fail(ZK_ERR_HIP, "zk_quotient_program_load: device allocation failed");
+            if (!upload_code(*hi) || !upload_code(*lo)) return ctx->fail(ZK_ERR_HIP, "zk_quotient_program_load: device allocation failed");
             P->part_hi = hi; P->part_lo = lo;
         }
     }
@@ -930,12 +875,9 @@ int quotient_program_load_gates(zk_ctx* ctx, const void* blob, size_t len, uint6
     uint32_t folds = 0;
     if (!rc) for (const uint4& ins : P->code) if (quot_is_fold(ins.x, ins.y)) folds++;
     if (!rc && (folds != *n_polys || P->uses_xpow)) rc = ctx->fail(ZK_ERR_PROGRAM, "gates program: %u folds for %u gate polynomials", folds, *n_polys);
-    if (!rc && (size_t)(P->n_slots > QUOT_NREG ? P->n_slots - QUOT_NREG : 0) * 64 * 32 > 160 * 1024)
-        rc = ctx->fail(ZK_ERR_LIMIT, "gates program needs %u live intermediates; this build keeps at most 80 in LDS", P->n_slots);
+    if (!rc && !quot_slots_fit(P->n_slots)) rc = slots_refused(ctx, *P);
     if (rc) { *n_polys = 0; return rc; }
-    hipError_t e = hipMalloc(&P->d_code, P->code.size() * 16 + 16);
-    if (e == hipSuccess) e = hipMemcpy(P->d_code, P->code.data(), P->code.size() * 16, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { *n_polys = 0; return ctx->fail(ZK_ERR_HIP, "gates program: device allocation failed"); }
+    if (!upload_code(*P)) { *n_polys = 0; return ctx->fail(ZK_ERR_HIP, "gates program: device allocation failed"); }
     *prog = ctx->next_handle++;
     ctx->programs[*prog] = P;
     return ZK_OK;
@@ -1010,32 +952,33 @@ void release_programs(zk_ctx* ctx) {
 
 int quotient_set_lds_attr() {
 #ifndef ZK_EMU
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUOT_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(quotient_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)QUOT_LDS_MAX);
 #endif
     return 0;
 }
 
-// coset < 0: the whole extended domain (columns of 2^extended_k rows).  coset = j >= 0: only coset j of it — the rows j, j + 2^(ek-k), ... —
-// with columns given as that coset's n = 2^k values (zk_coeff_to_coset_batch_dev); rotations then step by one row.  The 2^(ek-k) cosets are
-// independent, which is what lets a proof's quotient be split over GPUs: out receives the n numerator values of the coset.
-// row_count > 0: only rows [row_lo, row_lo + row_count) of that domain (the columns are complete, so rotations need no halo), out[i] = row row_lo + i —
-// the unit that lets more ranks than cosets share a quotient.
-// part: 0 = every identity; 1 / 2 = the high / low part of a program that has a degree split (QuotProgram::part_hi / part_lo).  low_cosets > 0 (part 2, coset < 0): the
-// columns are the whole extended domain but only the rows of its cosets 0 .. low_cosets-1 are evaluated — thread i of coset j reads row i * 2^(ek-k) + j — and
-// out receives low_cosets x n values, coset-major (what zk_cosets_to_pieces_dev takes).
-// rl: row-list mode (quotient.h, QuotRowList) — a program of extended_k = k that does not read X, on the whole domain.
-int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int coset, uint64_t row_lo, uint64_t row_count, int part, uint32_t low_cosets, int accumulate,
-                 const QuotRowList* rl) {
+// ---- one run (QuotRoute, quotient.h), job by job ------------------------------------------------
+namespace {
+
+// the program or degree part the route names, and whether the route is one that program can take
+int route_program(zk_ctx* ctx, uint64_t prog, const QuotRoute& r, const QuotProgram** whole, QuotProgram** run) {
     auto it = ctx->programs.find(prog);
     if (it == ctx->programs.end()) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: unknown program %llu", (unsigned long long)prog);
-    if (part && (!it->second->part_hi || !it->second->part_lo)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_part_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
-    QuotProgram& P = part == 1 ? *it->second->part_hi : part == 2 ? *it->second->part_lo : *it->second;
-    if (low_cosets && (part != 2 || coset >= 0 || row_count || (low_cosets & (low_cosets - 1)) || low_cosets > (1u << (P.ek - P.k))))
-        return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_low_dev: %u cosets of the extended domain: a power of two, at most 2^(extended_k - k), low part only", low_cosets);
-    if (rl && (coset >= 0 || row_count || part || low_cosets || accumulate || P.ek != P.k || P.uses_xpow || !rl->rows || !rl->bits || (uint64_t)rl->words * 32 < P.folds_taken))
+    if (r.part && (!it->second->part_hi || !it->second->part_lo)) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_part_dev: program %llu has no degree split (zk_quotient_program_split)", (unsigned long long)prog);
+    QuotProgram& P = r.part == 1 ? *it->second->part_hi : r.part == 2 ? *it->second->part_lo : *it->second;
+    if (r.low_cosets && (r.part != 2 || r.coset >= 0 || r.row_count || (r.low_cosets & (r.low_cosets - 1)) || r.low_cosets > (1u << (P.ek - P.k))))
+        return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_low_dev: %u cosets of the extended domain: a power of two, at most 2^(extended_k - k), low part only", r.low_cosets);
+    const QuotRowList* rl = r.rows;
+    if (rl && (r.coset >= 0 || r.row_count || r.part || r.low_cosets || r.accumulate || P.ek != P.k || P.uses_xpow || !rl->rows || !rl->bits || (uint64_t)rl->words * 32 < P.folds_taken))
         return ctx->fail(ZK_ERR_ARG, "quotient_run: a row list takes a program of extended_k = k that does not read X, on the whole domain");
-    if (rl && !rl->n) return ZK_OK;
+    *whole = it->second.get();
+    *run = &P;
+    return ZK_OK;
+}
+
+// the caller's arrays as the program's column table
+int bind_columns(zk_ctx* ctx, const QuotProgram& P, const zk_quotient_args* a, std::vector<const void*>& cols) {
     if (!a || !a->out || !a->l0 || !a->l_last || !a->l_active_row || !a->beta || !a->gamma || !a->theta || !a->y)
         return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: null argument");
     if (a->n_sets != P.n_sets) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: n_sets = %u but the program has %u permutation sets", a->n_sets, P.n_sets);
@@ -1043,8 +986,7 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
         (P.n_sets && !a->perm_products) || (P.n_lookups && (!a->lookup_product || !a->lookup_input || !a->lookup_table)) ||
         (P.n_challenges && !a->challenges))
         return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: missing column array");
-    // column pointer table
-    std::vector<const void*> cols(P.n_cols, nullptr);
+    cols.assign(P.n_cols, nullptr);
     for (uint32_t i = 0; i < P.n_fixed; i++) cols[P.col_fixed + i] = a->fixed[i];
     for (uint32_t i = 0; i < P.n_advice; i++) cols[P.col_advice + i] = a->advice[i];
     for (uint32_t i = 0; i < P.n_instance; i++) cols[P.col_instance + i] = a->instance[i];
@@ -1055,104 +997,139 @@ int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, int cose
         cols[P.col_lk_z + i] = a->lookup_product[i]; cols[P.col_lk_a + i] = a->lookup_input[i]; cols[P.col_lk_s + i] = a->lookup_table[i];
     }
     for (auto p : cols) if (!p) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_dev: null column pointer");
-    // constants of this run
+    return ZK_OK;
+}
+
+u256 pow_u32(u256 base, uint32_t e) {        // square and multiply on the host: a few dozen products per run
+    u256 acc = Fr::one();
+    for (; e; e >>= 1) { if (e & 1) acc = Fr::mul(acc, base); base = Fr::sqr(base); }
+    return acc;
+}
+
+// the constants of this run, in the layout compile_program fixed (QuotProgram::c_*).  acc_folds > 0: accumulate mode, y^acc_folds last (QuotArgs::acc_const)
+std::vector<u256> run_constants(const QuotProgram& P, const zk_quotient_args* a, bool accumulate, uint32_t acc_folds) {
     auto rd = [](const void* p) { u256 o; memcpy(&o, p, 32); return o; };
-    std::vector<u256> consts(P.n_consts + (accumulate ? 1 : 0));            // (accumulate mode: y^E last)
+    std::vector<u256> consts(P.n_consts + (accumulate ? 1 : 0));
     for (size_t i = 0; i < P.graph_consts.size(); i++) consts[i] = P.graph_consts[i];
     consts[P.c_zero] = Fr::zero(); consts[P.c_one] = Fr::one();
     for (uint32_t i = 0; i < P.n_challenges; i++) consts[P.c_chal + i] = rd((const char*)a->challenges + 32 * i);
-    const u256 beta = rd(a->beta);
-    consts[P.c_beta] = beta; consts[P.c_gamma] = rd(a->gamma); consts[P.c_theta] = rd(a->theta); consts[P.c_y] = rd(a->y);
-    for (size_t i = 0; i < P.ypow_exps.size(); i++) {                 // y^e for the folds that follow skipped identities (square and multiply on the host: a few dozen products)
-        u256 acc = Fr::one(), base = consts[P.c_y];
-        for (uint32_t e = P.ypow_exps[i]; e; e >>= 1) { if (e & 1) acc = Fr::mul(acc, base); base = Fr::sqr(base); }
-        consts[P.c_ypow + i] = acc;
-    }
-    if (accumulate) {                                                 // E = every identity of the WHOLE program, also for a degree part: high + low still sum to previous * y^E + numerator
-        u256 acc = Fr::one(), base = consts[P.c_y];
-        for (uint32_t e = it->second->folds_taken; e; e >>= 1) { if (e & 1) acc = Fr::mul(acc, base); base = Fr::sqr(base); }
-        consts[P.n_consts] = acc;
-    }
-    {   // delta_j = beta * ZETA * DELTA^j  (current_delta of evaluate_h without the omega^idx factor)
-        const uint64_t zl[4] = BN254_FR_ZETA_M, dl[4] = BN254_FR_DELTA_M;
-        u256 zeta, delta;
-        for (int i = 0; i < 8; i++) { zeta.v[i] = (uint32_t)(zl[i >> 1] >> (32 * (i & 1))); delta.v[i] = (uint32_t)(dl[i >> 1] >> (32 * (i & 1))); }
-        u256 cur = Fr::mul(beta, zeta);
-        for (uint32_t j = 0; j < P.n_perm_cols; j++) { consts[P.c_delta + j] = cur; cur = Fr::mul(cur, delta); }
-    }
-    if (coset >= (int)(1u << (P.ek - P.k))) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_dev: coset %d out of range", coset);
-    const bool cm = coset >= 0;
-    const uint32_t size_log = cm ? P.k : P.ek;
-    const uint64_t size = 1ull << size_log;
-    const int64_t rot_scale = cm ? 1 : 1ll << (P.ek - P.k);
+    const u256 beta = rd(a->beta), y = rd(a->y);
+    consts[P.c_beta] = beta; consts[P.c_gamma] = rd(a->gamma); consts[P.c_theta] = rd(a->theta); consts[P.c_y] = y;
+    for (size_t i = 0; i < P.ypow_exps.size(); i++) consts[P.c_ypow + i] = pow_u32(y, P.ypow_exps[i]);    // y^e for the folds that follow skipped identities
+    if (accumulate) consts[P.n_consts] = pow_u32(y, acc_folds);
+    // delta_j = beta * ZETA * DELTA^j  (current_delta of evaluate_h without the omega^idx factor)
+    const uint64_t zl[4] = BN254_FR_ZETA_M, dl[4] = BN254_FR_DELTA_M;
+    u256 zeta, delta;
+    for (int i = 0; i < 8; i++) { zeta.v[i] = (uint32_t)(zl[i >> 1] >> (32 * (i & 1))); delta.v[i] = (uint32_t)(dl[i >> 1] >> (32 * (i & 1))); }
+    u256 cur = Fr::mul(beta, zeta);
+    for (uint32_t j = 0; j < P.n_perm_cols; j++) { consts[P.c_delta + j] = cur; cur = Fr::mul(cur, delta); }
+    return consts;
+}
+
+// the program's rotations as row offsets of a domain of 2^size_log rows, `scale` rows per rotation step: non-negative, below the size
+std::vector<uint32_t> rotation_offsets(const QuotProgram& P, uint32_t size_log, int64_t scale) {
+    const int64_t size = 1ll << size_log;
     std::vector<uint32_t> rot_off(P.rotations.size() + 1, 0);
     for (size_t i = 0; i < P.rotations.size(); i++) {
-        int64_t v = ((int64_t)P.rotations[i] * rot_scale) % (int64_t)size;
-        if (v < 0) v += (int64_t)size;
+        int64_t v = ((int64_t)P.rotations[i] * scale) % size;
+        if (v < 0) v += size;
         rot_off[i] = (uint32_t)v;
     }
-    hipStream_t st = ctx->stream;
-    // the run's constants | column pointers | rotation offsets, in this context's own buffer
-    const size_t off_cols = ((size_t)consts.size() * 32 + 32 + 255) & ~(size_t)255, off_rot = (off_cols + (size_t)P.n_cols * sizeof(void*) + 8 + 255) & ~(size_t)255;
-    ZK_HIP(ctx->ws_quot.ensure(off_rot + (P.rotations.size() + 1) * 4));
-    void* const d_consts = ctx->ws_quot.p;
-    void* const d_cols = (char*)ctx->ws_quot.p + off_cols;
-    void* const d_rot = (char*)ctx->ws_quot.p + off_rot;
-    ZK_HIP(hipMemcpyAsync(d_consts, consts.data(), consts.size() * 32, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(d_cols, cols.data(), cols.size() * sizeof(void*), hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(d_rot, rot_off.data(), rot_off.size() * 4, hipMemcpyHostToDevice, st));
-    QuotArgs q;
-    memset(&q, 0, sizeof q);
-    q.code = (const uint4*)P.d_code; q.n_instr = (uint32_t)P.code.size(); q.consts = d_consts;
-    q.cols = (const void* const*)d_cols; q.rot_off = (const uint32_t*)d_rot; q.size_log = size_log; q.out = a->out;
-    q.uses_xpow = P.uses_xpow ? 1 : 0;
-    q.accumulate = accumulate ? 1u : 0u; q.acc_const = P.n_consts;
+    return rot_off;
+}
+
+// the run's constants | column pointers | rotation offsets into this context's own buffer, and their addresses into q
+int upload_tables(zk_ctx* ctx, const std::vector<u256>& consts, const std::vector<const void*>& cols, const std::vector<uint32_t>& rot_off, QuotArgs& q) {
+    const size_t off_cols = ((size_t)consts.size() * 32 + 32 + 255) & ~(size_t)255, off_rot = (off_cols + cols.size() * sizeof(void*) + 8 + 255) & ~(size_t)255;
+    ZK_HIP(ctx->ws_quot.ensure(off_rot + rot_off.size() * 4));
+    char* const base = (char*)ctx->ws_quot.p;
+    ZK_HIP(hipMemcpyAsync(base, consts.data(), consts.size() * 32, hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(base + off_cols, cols.data(), cols.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(base + off_rot, rot_off.data(), rot_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    q.consts = base; q.cols = (const void* const*)(base + off_cols); q.rot_off = (const uint32_t*)(base + off_rot);
+    return ZK_OK;
+}
+
+// the route as the kernels read it (QuotArgs: X power, strided rows, row slice); *rows = the rows this run evaluates
+int route_args(zk_ctx* ctx, const QuotProgram& P, const QuotRoute& r, QuotArgs& q, uint64_t* rows) {
+    const bool cm = r.coset >= 0;
     q.xpow_mul = cm ? 1u << (P.ek - P.k) : 1u;
-    q.xpow_add = cm ? (uint32_t)coset : 0u;
+    q.xpow_add = cm ? (uint32_t)r.coset : 0u;
+    q.uses_xpow = P.uses_xpow ? 1 : 0;
     if (P.uses_xpow) {
         int rc = ntt_pow_tables(ctx, P.ek, domain_omega(P.ek), &q.tw_lo, &q.tw_hi, &q.lo_bits);
         if (rc) return rc;
     }
-    uint64_t rows = size;
-    if (low_cosets) {
-        rows = (uint64_t)low_cosets << P.k;
+    const uint64_t size = 1ull << q.size_log;
+    *rows = size;
+    if (r.low_cosets) {
+        *rows = (uint64_t)r.low_cosets << P.k;
         q.sub_log = 0;
-        while ((1u << q.sub_log) < low_cosets) q.sub_log++;
+        while ((1u << q.sub_log) < r.low_cosets) q.sub_log++;
         q.stride_log = P.ek - P.k; q.k_log = P.k; q.strided = 1;
     }
-    if (row_count) {
-        if (row_lo + row_count > size || (row_count & (row_count - 1)) || row_lo % row_count)
+    if (r.row_count) {
+        if (r.row_lo + r.row_count > size || (r.row_count & (r.row_count - 1)) || r.row_lo % r.row_count)
             return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_rows_dev: rows [%llu, +%llu) must be an aligned power-of-two slice of the %llu rows",
-                             (unsigned long long)row_lo, (unsigned long long)row_count, (unsigned long long)size);
-        rows = row_count;
-        q.row_base = (uint32_t)row_lo;
+                             (unsigned long long)r.row_lo, (unsigned long long)r.row_count, (unsigned long long)size);
+        *rows = r.row_count;
+        q.row_base = (uint32_t)r.row_lo;
     }
-    uint32_t T = (uint32_t)std::min(ctx->tune.quot_threads, 256);     // the kernel is compiled for <= 256 threads per workgroup
-    if (T > rows) T = (uint32_t)rows;
-    const uint32_t lds_slots = P.n_slots > QUOT_NREG ? P.n_slots - QUOT_NREG : 0;
-    while (T > 64 && (size_t)lds_slots * T * 32 > 32 * 1024) T >>= 1;
-    if (T < 1) T = 1;
-    const size_t lds = (size_t)lds_slots * T * 32;
-    if (lds > 160 * 1024) return ctx->fail(ZK_ERR_LIMIT, "quotient program needs %zu bytes of LDS", lds);
+    return ZK_OK;
+}
+
+// shape, launch, time
+int launch(zk_ctx* ctx, const QuotProgram& P, const QuotArgs& q, uint64_t rows, const QuotRowList* rl) {
+    const QuotShape s = quot_launch_shape(P.n_slots, ctx->tune.quot_threads, rows);
+    if (s.lds_bytes > QUOT_LDS_MAX) return ctx->fail(ZK_ERR_LIMIT, "quotient program needs %zu bytes of LDS", s.lds_bytes);
     EvTimer tq(ctx, "quotient");
     if (rl) {
-        ZK_LAUNCH(quotient_rows_kernel, (rl->n + T - 1) / T, T, lds, st, q, rl->rows, rl->n, rl->bits, rl->words);
+        ZK_LAUNCH(quotient_rows_kernel, (rl->n + s.threads - 1) / s.threads, s.threads, s.lds_bytes, ctx->stream, q, rl->rows, rl->n, rl->bits, rl->words);
         ZK_CHECK_LAUNCH();
-    } else if (quot_jit_ready(P)) {                                          // (the PROGRAM records whether it was generated: contexts that borrow it need no tunable of their own)
-        uint32_t Tj = (uint32_t)std::min(ctx->tune.quot_threads, 256);
-        if (Tj > rows) Tj = (uint32_t)rows;
-        int rcj = quot_jit_launch(ctx, P, q, rows, Tj);
-        if (rcj) return rcj;
+    } else if (quot_jit_ready(P)) {                       // (the PROGRAM records whether it was generated: contexts that borrow it need no tunable of their own)
+        // generated kernels hold their slots in registers: the shape of a program without LDS slots, min(quot_threads, 256, rows) and no halving
+        int rc = quot_jit_launch(ctx, P, q, rows, quot_launch_shape(0, ctx->tune.quot_threads, rows).threads);
+        if (rc) return rc;
     } else {
-        ZK_LAUNCH(quotient_kernel, (uint32_t)(rows / T), T, lds, st, q);
+        ZK_LAUNCH(quotient_kernel, (uint32_t)(rows / s.threads), s.threads, s.lds_bytes, ctx->stream, q);
         ZK_CHECK_LAUNCH();
     }
     tq.stop();
-    ZK_HIP(hipStreamSynchronize(st));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
     tq.resolve();
+    return ZK_OK;
+}
+
+}  // namespace
+
+int quotient_run(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* a, const QuotRoute& r) {
+    const QuotProgram* whole = nullptr;
+    QuotProgram* run = nullptr;
+    int rc = route_program(ctx, prog, r, &whole, &run);
+    if (rc) return rc;
+    const QuotProgram& P = *run;
+    if (r.rows && !r.rows->n) return ZK_OK;
+    std::vector<const void*> cols;
+    rc = bind_columns(ctx, P, a, cols);
+    if (rc) return rc;
+    // accumulate mode: E = every identity of the WHOLE program, also for a degree part: high + low still sum to previous * y^E + numerator
+    const std::vector<u256> consts = run_constants(P, a, r.accumulate, whole->folds_taken);
+    if (r.coset >= (int)(1u << (P.ek - P.k))) return ctx->fail(ZK_ERR_ARG, "zk_quotient_run_coset_dev: coset %d out of range", r.coset);
+    QuotArgs q;
+    memset(&q, 0, sizeof q);
+    q.code = (const uint4*)P.d_code; q.n_instr = (uint32_t)P.code.size(); q.out = a->out;
+    q.accumulate = r.accumulate ? 1u : 0u; q.acc_const = P.n_consts;
+    q.size_log = r.coset >= 0 ? P.k : P.ek;                           // a coset's columns hold its own n rows, and a rotation steps by one of them
+    rc = upload_tables(ctx, consts, cols, rotation_offsets(P, q.size_log, r.coset >= 0 ? 1 : 1ll << (P.ek - P.k)), q);
+    if (rc) return rc;
+    uint64_t rows = 0;
+    rc = route_args(ctx, P, r, q, &rows);
+    if (rc) return rc;
+    rc = launch(ctx, P, q, rows, r.rows);
+    if (rc) return rc;
     // every column once + the output, per row of the extended domain — counted once per evaluation of h's numerator (on its high part when the program is split; the
     // theta-compression programs of the lookups, which run on this interpreter too, are not part of that figure though their time is inside the "quotient" timer)
-    if (ctx->timing && P.ek > P.k && part != 2) ctx->last_ms["quotient_alg_bytes"] += (double)rows * (P.n_cols + 1) * 32.0;
+    if (ctx->timing && P.ek > P.k && r.part != 2) ctx->last_ms["quotient_alg_bytes"] += (double)rows * (P.n_cols + 1) * 32.0;
     return ZK_OK;
 }
 
@@ -1301,7 +1278,7 @@ int evaluate_h_host(zk_ctx* ctx, uint64_t pkh, const void* const* advice, const 
     qa.lookup_product = dyn + P.n_advice + P.n_instance + P.n_sets;
     qa.lookup_input = qa.lookup_product + P.n_lookups; qa.lookup_table = qa.lookup_input + P.n_lookups;
     qa.challenges = challenges; qa.beta = beta; qa.gamma = gamma; qa.theta = theta; qa.y = y; qa.out = pk->h_ext;
-    int rc = quotient_run(ctx, pk->prog, &qa, -1, 0, 0, 0, 0, 0);
+    int rc = quotient_run(ctx, pk->prog, &qa, QuotRoute{});
     if (rc) return rc;
     size_t out_bytes = (size_t)32 << P.ek;
     if (finish) {
