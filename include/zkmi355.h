@@ -52,10 +52,10 @@ typedef struct zk_ctx zk_ctx;
  * call instead of handing the library bytes past the end of its object.  Fields are only ever APPENDED, and each append bumps ZK_ABI_VERSION; a binding
  * asserts at start-up that zk_abi_version() is the ZK_ABI_VERSION it was written against and that zk_abi_struct_size(name) equals its own size of every
  * struct it declares (shim/halo2_proofs_mi355x/src/mi355x.rs does; tests/test_shim_abi.py diffs the declarations field by field). */
-#define ZK_ABI_VERSION 6u
+#define ZK_ABI_VERSION 7u
 uint32_t zk_abi_version(void);
-/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure", "zk_plonk_phases") in this build of the library; 0 for an
- * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify). */
+/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure", "zk_plonk_phases", "zk_plonk_keygen_desc") in this build of the library; 0 for an
+ * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify), version 7 the keygen descriptor (zk_plonk_keygen_vk). */
 uint32_t zk_abi_struct_size(const char* struct_name);
 #define ZK_STRUCT_INIT(s) do { memset(&(s), 0, sizeof(s)); (s).struct_size = (uint32_t)sizeof(s); } while (0)   /* needs <string.h> */
 
@@ -552,6 +552,40 @@ int zk_mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* desc, zk_mock_failure
  * every blob must declare exactly n_challenges challenges (ZK_ERR_ARG otherwise); n_challenges = 0 takes what zk_mock_prover_verify takes. */
 int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const void* challenges, uint32_t n_challenges, zk_mock_failure* out, size_t cap,
                                  uint64_t counts[3], size_t* n_written);
+
+/* ---- keygen: halo2_proofs::plonk::{keygen_vk, keygen_pk} after synthesis (src/plonk/keygen.rs; reference call sites circuits/src/sgx_dcap_verifier.rs:803,807) --------- *
+ * zk_plonk_keygen_vk: from the fixed columns as halo2 holds them after selector compression and the copy mapping of permutation::keygen::Assembly (two u32 planes,
+ * exactly as zk_mock_desc carries them) it builds on the device what keygen_vk builds on the CPU: the permutation columns
+ *   sigma_j[i] = DELTA^(perm_map_column[j * 2^k + i]) * omega^(perm_map_row[j * 2^k + i])      (Assembly::build_vk / build_pk; omega the 2^k domain generator)
+ * and the commitments of all n_fixed + n_perm_columns Lagrange columns, one batched MSM on srs_g_lagrange (the table of params.g_lagrange, 2^k points).
+ * fixed_commitments / permutation_commitments receive normalised points in zk_msm's 96-byte form; an all-zero fixed column gives the identity (0, 0, 0), as halo2's
+ * vk allows.  n_fixed = 0 and n_perm_columns = 0 are legal (their output pointer may then be NULL).  *kg receives a handle that keeps the Lagrange columns in HBM.
+ * ZK_ERR_ARG, with nothing written to the outputs: a wrong struct_size, k outside 1 .. 27, a NULL array or column, a mapping entry with column >= n_perm_columns
+ * or row >= 2^k (zk_last_error names the first such cell), a mapping that is not a permutation of the cells (zk_last_error gives the number of cells whose image
+ * another cell already has) - halo2 cannot produce either, a C caller can, and a key built from one proves nothing; an srs_g_lagrange that is not a registered
+ * table of exactly 2^k points (a rank's slice of a sharded SRS included).  ZK_ERR_LIMIT: 2^32 mapping cells or more.
+ * With values_on_device the fixed columns are DEVICE pointers, borrowed: they must outlive the handle and every key built from it.
+ * The two calls follow halo2: vk.transcript_repr hashes the commitments, so the caller computes it between them and passes it in host->transcript_repr.
+ * zk_plonk_keygen_pk: zk_plonk_pk_build_phased (phases = NULL: zk_plonk_pk_build) on the handle's resident columns - no second upload, sigma is not recomputed.
+ * host->fixed_values and host->sigma_values must be NULL and host->k / n_fixed / n_perm_columns those of the handle (ZK_ERR_ARG otherwise); host->values_on_device is
+ * ignored; a sharded key (host->shard_world > 1, or a table slice: srs_g_lagrange not of exactly 2^k points, srs_g of fewer) is ZK_ERR_ARG: keygen runs on one GPU with the whole table.  The key is a key like any other (zk_plonk_pk_share /
+ * _release / _descriptor / zk_plonk_prove*).  The columns belong to the handle AND to every key built from it: they are freed when the last of those has been released,
+ * in either order.  zk_plonk_keygen_columns: the device pointers of the Lagrange columns (n_fixed, n_perm_columns entries), valid while the handle lives.
+ * Handles are per context: zk_ctx_destroy releases those the context still holds.  Timing labels (zk_timing_get): "keygen_mapping_check", "keygen_sigma".
+ * Tunable "keygen_wgs": the workgroups (of 256 cells per step) the two kernels launch at most, 2048 by default; the cells beyond are a grid stride. */
+typedef struct zk_plonk_keygen_desc zk_plonk_keygen_desc;
+struct zk_plonk_keygen_desc {
+    uint32_t struct_size;                       /* sizeof(zk_plonk_keygen_desc) of the caller (ABI versioning) */
+    uint32_t k, n_fixed, n_perm_columns;
+    const void* const* fixed_values;            /* n_fixed columns, 2^k x 32 B Montgomery (selectors already compressed); HOST, or DEVICE with values_on_device */
+    const uint32_t* perm_map_column;            /* n_perm_columns x 2^k, HOST, exactly as zk_mock_desc */
+    const uint32_t* perm_map_row;
+    uint32_t values_on_device;
+};
+int zk_plonk_keygen_vk(zk_ctx* ctx, const zk_plonk_keygen_desc* desc, uint64_t srs_g_lagrange, void* fixed_commitments, void* permutation_commitments, uint64_t* kg);
+int zk_plonk_keygen_columns(zk_ctx* ctx, uint64_t kg, const void** fixed_dev, const void** sigma_dev);
+int zk_plonk_keygen_pk(zk_ctx* ctx, uint64_t kg, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk);
+int zk_plonk_keygen_release(zk_ctx* ctx, uint64_t kg);
 
 /* library / build identification */
 const char* zk_version(void);

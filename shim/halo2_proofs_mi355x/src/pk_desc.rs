@@ -88,6 +88,10 @@ pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Aff
     if let Some(h) = map.get(&id) {
         return Some(*h);
     }
+    // keygen_native.patch: when keygen_vk of this (params, vk) ran in the library, its Lagrange columns are still in HBM under a keygen handle, filed by what survives
+    // every move of the ProvingKey between keygen_pk and here — (params.g_lagrange, vk.transcript_repr).  The key is then built on them (zk_plonk_keygen_pk: no upload,
+    // sigma not recomputed).  Taken only after the cache miss above, so a handle is never taken without being consumed (keygen_native::keygen_pk releases it either way).
+    let keygen = crate::keygen_native::take(params.g_lagrange.as_ptr() as usize, pk.vk.transcript_repr.to_repr());
     let cs = &pk.vk.cs;
     // [3P-MEM] sealed::Phase(u8): advice_column_phase[c] / challenge_phase[i] in 0 ..= 2
     let advice_phase: Vec<u8> = cs.advice_column_phase.iter().map(|p| p.0).collect();
@@ -144,6 +148,15 @@ pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Aff
         n_advice: advice_phase.len() as u32, advice_phase: advice_phase.as_ptr(),
         n_challenges: challenge_phase.len() as u32, challenge_phase: challenge_phase.as_ptr(),
     };
+    if let Some(kg) = keygen {
+        // on a keygen handle the columns are the handle's: zk_plonk_keygen_pk wants both arrays null (every field of the struct is Copy: `host` stays whole)
+        let on_handle = ZkPlonkPkHost { fixed_values: std::ptr::null(), sigma_values: std::ptr::null(), ..host };
+        if let Some(key) = crate::keygen_native::keygen_pk(g, kg, &on_handle, if phased { Some(&phases) } else { None }, srs_g, srs_gl) {
+            map.insert(id, key);
+            return Some(key);
+        }
+        // (reported through Gpu::complain, the handle released: the key is built from the host columns as if keygen_vk had run on the CPU)
+    }
     let rc = if phased { unsafe { zk_plonk_pk_build_phased(g.ctx, &host, &phases, srs_g, srs_gl, &mut handle) } } else { unsafe { zk_plonk_pk_build(g.ctx, &host, srs_g, srs_gl, &mut handle) } };
     if rc != 0 {
         g.complain(if phased { "zk_plonk_pk_build_phased" } else { "zk_plonk_pk_build" });
@@ -155,6 +168,7 @@ pub fn key_for(g: &'static Gpu, params: &ParamsKZG<Bn256>, pk: &ProvingKey<G1Aff
 
 /// Drop the device copy of a key (e.g. from `impl Drop for ProvingKey`, or when a long-lived service rotates circuits).
 pub fn forget(pk: &ProvingKey<G1Affine>) {
+    crate::keygen_native::forget(pk.vk.transcript_repr.to_repr());   // a keygen handle no proof has consumed yet
     let (Some(g), Ok(mut guard)) = (gpu(), KEYS.lock()) else { return };
     if let Some(map) = guard.as_mut() {
         let addr = pk as *const _ as usize;

@@ -26,7 +26,7 @@ class ZkError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 6          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
+ABI_VERSION = 7          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
 
 
 class QuotientArgs(C.Structure):
@@ -58,6 +58,12 @@ class PlonkPhases(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_advice", C.c_uint32), ("advice_phase", C.c_void_p), ("n_challenges", C.c_uint32), ("challenge_phase", C.c_void_p)]
 
 
+class KeygenDesc(C.Structure):
+    """zk_plonk_keygen_desc (zk_plonk_keygen_vk)"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("n_fixed", C.c_uint32), ("n_perm_columns", C.c_uint32),
+                ("fixed_values", C.c_void_p), ("perm_map_column", C.c_void_p), ("perm_map_row", C.c_void_p), ("values_on_device", C.c_uint32)]
+
+
 PHASE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))     # zk_phase_fn
 
 
@@ -82,7 +88,7 @@ def _load(path: str):
         raise RuntimeError(f"{path}: ABI version {lib.zk_abi_version()}, this binding is written against {ABI_VERSION} (rebuild: __graft_entry__.build())")
     if lib.zk_abi_struct_size(b"zk_quotient_args") != C.sizeof(QuotientArgs):
         raise RuntimeError(f"{path}: sizeof(zk_quotient_args) = {lib.zk_abi_struct_size(b'zk_quotient_args')}, the binding's QuotientArgs has {C.sizeof(QuotientArgs)}")
-    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure), (b"zk_plonk_phases", PlonkPhases)):
+    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure), (b"zk_plonk_phases", PlonkPhases), (b"zk_plonk_keygen_desc", KeygenDesc)):
         if lib.zk_abi_struct_size(name) != C.sizeof(st):
             raise RuntimeError(f"{path}: sizeof({name.decode()}) = {lib.zk_abi_struct_size(name)}, the binding's {st.__name__} has {C.sizeof(st)}")
     return lib
@@ -558,6 +564,46 @@ class Backend:
                                                            counts, C.byref(written)))
         recs = [(f.kind, f.index, f.row, f.other_column, f.other_row) for f in out[: written.value]]
         return recs, (int(counts[0]), int(counts[1]), int(counts[2]))
+
+    # -- keygen ----------------------------------------------------------------------------------
+    def plonk_keygen_vk(self, k: int, fixed, perm_map_column, perm_map_row, srs_g_lagrange: int, struct_size: int | None = None, out=None):
+        """zk_plonk_keygen_vk.  fixed: (2^k, 4) uint64 Montgomery arrays (host) or device buffers, all of one kind; perm_map_column / perm_map_row:
+        (n_perm_columns, 2^k) integer arrays (Assembly.map_c / map_r; None or empty = no permutation columns).  Returns (fixed commitments (n_fixed, 12),
+        permutation commitments (n_perm_columns, 12), keygen handle); `out` = (two uint64 arrays): receive the points instead of fresh arrays."""
+        n = 1 << k
+        on_device = any(not isinstance(c, np.ndarray) for c in fixed)
+        cols = list(fixed) if on_device else [np.ascontiguousarray(c, dtype=np.uint64).reshape(n, 4) for c in fixed]
+        mc = np.ascontiguousarray(np.asarray(perm_map_column if perm_map_column is not None else []).astype(np.uint32, copy=False)).reshape(-1)
+        mr = np.ascontiguousarray(np.asarray(perm_map_row if perm_map_row is not None else []).astype(np.uint32, copy=False)).reshape(-1)
+        assert mc.size == mr.size and mc.size % n == 0
+        m = mc.size // n
+        d = KeygenDesc()
+        d.struct_size = C.sizeof(KeygenDesc) if struct_size is None else struct_size
+        d.k, d.n_fixed, d.n_perm_columns, d.values_on_device = k, len(cols), m, 1 if on_device else 0
+        arr = (C.c_void_p * max(1, len(cols)))(*[_dptr(c) if on_device else c.ctypes.data for c in cols])
+        d.fixed_values = C.cast(arr, C.c_void_p).value if cols else None
+        d.perm_map_column, d.perm_map_row = (mc.ctypes.data, mr.ctypes.data) if m else (None, None)
+        fc, pc = out if out is not None else (np.zeros((len(cols), 12), dtype=np.uint64), np.zeros((m, 12), dtype=np.uint64))
+        kg = C.c_uint64()
+        self._ck(self.lib.zk_plonk_keygen_vk(self.ctx, C.byref(d), C.c_uint64(srs_g_lagrange), fc.ctypes.data_as(C.c_void_p) if fc.size else None,
+                                             pc.ctypes.data_as(C.c_void_p) if pc.size else None, C.byref(kg)))
+        return fc, pc, kg.value
+
+    def plonk_keygen_columns(self, kg: int, n_fixed: int, n_perm_columns: int):
+        """zk_plonk_keygen_columns: the device pointers (ints) of the handle's Lagrange columns, valid while the handle lives"""
+        fx, sg = (C.c_void_p * max(1, n_fixed))(), (C.c_void_p * max(1, n_perm_columns))()
+        self._ck(self.lib.zk_plonk_keygen_columns(self.ctx, C.c_uint64(kg), fx, sg))
+        return [int(fx[i] or 0) for i in range(n_fixed)], [int(sg[j] or 0) for j in range(n_perm_columns)]
+
+    def plonk_keygen_pk(self, kg: int, host, phases, srs_g: int, srs_g_lagrange: int) -> int:
+        """zk_plonk_keygen_pk: host = plonk.native.PkHost with fixed_values / sigma_values NULL, phases = PlonkPhases or None; returns the key handle"""
+        out = C.c_uint64()
+        self._ck(self.lib.zk_plonk_keygen_pk(self.ctx, C.c_uint64(kg), C.byref(host), C.byref(phases) if phases is not None else None, C.c_uint64(srs_g),
+                                             C.c_uint64(srs_g_lagrange), C.byref(out)))
+        return out.value
+
+    def plonk_keygen_release(self, kg: int):
+        self._ck(self.lib.zk_plonk_keygen_release(self.ctx, C.c_uint64(kg)))
 
     # -- quotient -------------------------------------------------------------------------------
     def quotient_program_load(self, blob: bytes) -> int:

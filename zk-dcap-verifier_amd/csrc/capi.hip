@@ -150,6 +150,7 @@ uint32_t zk_abi_struct_size(const char* name) ZK_ABI_TRY {
     if (!strcmp(name, "zk_mock_desc")) return (uint32_t)sizeof(zk_mock_desc);
     if (!strcmp(name, "zk_mock_failure")) return (uint32_t)sizeof(zk_mock_failure);
     if (!strcmp(name, "zk_plonk_phases")) return (uint32_t)sizeof(zk_plonk_phases);
+    if (!strcmp(name, "zk_plonk_keygen_desc")) return (uint32_t)sizeof(zk_plonk_keygen_desc);
     return 0;
 } ZK_ABI_CATCH_VALUE(nullptr, 0u)
 
@@ -267,7 +268,7 @@ static int* tune_slot(zk_ctx* ctx, const char* key) {
         {"ntt_tile_log", &t.ntt_tile_log}, {"ntt_threads", &t.ntt_threads}, {"ntt_max_radix_log", &t.ntt_max_radix_log}, {"ntt_plan", &t.ntt_plan}, {"ntt_full_twiddle_max_log", &t.ntt_full_twiddle_max_log}, {"ntt_coset_table", &t.ntt_coset_table}, {"ntt_col_major", &t.ntt_col_major},
         {"vec_block", &t.vec_block}, {"quot_threads", &t.quot_threads},
         {"ntt_quarter_input", &t.ntt_quarter_input}, {"ntt_fuse_scale", &t.ntt_fuse_scale}, {"quot_piece_cosets", &t.quot_piece_cosets}, {"quot_factor_horner", &t.quot_factor_horner}, {"quot_degree_split", &t.quot_degree_split}, {"quot_group_factors", &t.quot_group_factors}, {"ntt_ws_limit_mb", &t.ntt_ws_limit_mb}, 
-        {"quot_jit", &t.quot_jit}, {"quot_jit_group", &t.quot_jit_group}, {"quot_jit_waves", &t.quot_jit_waves}, {"quot_remat_ops", &t.quot_remat_ops}, {"quot_remat_distance", &t.quot_remat_distance}};
+        {"quot_jit", &t.quot_jit}, {"quot_jit_group", &t.quot_jit_group}, {"quot_jit_waves", &t.quot_jit_waves}, {"quot_remat_ops", &t.quot_remat_ops}, {"quot_remat_distance", &t.quot_remat_distance}, {"keygen_wgs", &t.keygen_wgs}};
     for (auto& e : tab) if (!strcmp(e.k, key)) return e.v;
     return nullptr;
 }

@@ -2,21 +2,35 @@
 // The device half of keygen_pk, written — like create_proof (prover.hip) — as a CLIENT of the public entry points: upload the Lagrange columns, lagrange_to_coeff,
 // coeff_to_extended, l0 / l_last / l_active_row, load the ZKQ1 programs.  One PkMem per key per process (columns + the host arrays the descriptor points into);
 // every holding context has a PkHandle with its own program handles (zk_quotient_program_share) and SRS handles.
+//
+// Keygen (zk_plonk_keygen_vk / _pk, at the end of this file) is the one part that is NOT a client: its two kernels — mapping_check and sigma_from_mapping — are
+// launched here on the context's stream, under the context's lock, like every other kernel of the library.
 #include <string.h>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
-#include "field.cuh"
-#include "../../include/zkmi355.h"
-#include "abi_guard.h"
+#include "ctx.h"
+#include "bn254_consts.h"
 #include "plonk_shared.h"
 
 using namespace zk;
+namespace zk { u256 domain_omega(uint32_t k); }                       // ntt.hip
 
 #define PK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
 namespace {
+struct KgCols {                                                       // the Lagrange columns of a keygen handle (zk_plonk_keygen_vk): shared by the handle and every key built
+    int device = 0;                                                   // from it (zk_plonk_keygen_pk), freed with the last of them, whichever that is
+    std::vector<void*> owned;
+    ~KgCols() {
+        if (owned.empty()) return;
+        (void)hipSetDevice(device);
+        for (void* p : owned) (void)hipFree(p);
+    }
+};
 struct PkMem {
+    std::shared_ptr<KgCols> keygen_cols;                              // a key of zk_plonk_keygen_pk: its fixed / sigma values are these (not in `owned`)
     std::vector<void*> owned;                                         // device allocations, freed by whoever drops the last handle
     std::vector<const void*> fixed_values, fixed_polys, fixed_cosets, sigma_values, sigma_polys, sigma_cosets;
     void* l[3] = {nullptr, nullptr, nullptr};
@@ -99,7 +113,8 @@ static int check_phases(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plon
     return ZK_OK;
 }
 
-static int pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk) {
+static int pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange, uint64_t* pk,
+                    const std::shared_ptr<KgCols>& keygen_cols = nullptr) {
     if (!ctx || !host || !pk) return ZK_ERR_ARG;
     if (host->struct_size != sizeof(zk_plonk_pk_host))
         return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_pk_build: zk_plonk_pk_host.struct_size %u, expected %zu (ABI version %u)", host->struct_size, sizeof(zk_plonk_pk_host), ZK_ABI_VERSION);
@@ -121,6 +136,7 @@ static int pk_build(zk_ctx* ctx, const zk_plonk_pk_host* host, const zk_plonk_ph
     h->mem = new PkMem();
     h->mem->holders = 1;
     PkMem* m = h->mem;
+    m->keygen_cols = keygen_cols;
     auto alloc = [&](size_t bytes) -> void* {
         m->owned.reserve(m->owned.size() + 1);                         // (the slot first: a buffer is never allocated without an owner to free it)
         void* p = nullptr;
@@ -332,6 +348,217 @@ extern "C" int zk_plonk_prove_phased(zk_ctx* ctx, uint64_t pk, uint32_t n_circui
                           true, advice, next_phase, next_phase_user);
 } ZK_ABI_CATCH(ctx)
 
+// ---- keygen: keygen_vk + keygen_pk after synthesis (include/zkmi355.h, zk_plonk_keygen_vk) ---------------------------------------------------------------------
+// halo2's permutation::keygen::Assembly::build_vk / build_pk: sigma_j[i] = DELTA^c * omega^r for (c, r) = mapping[j][i].  A table of all omega^r would be n x 32 B per
+// key and every cell a random 32-byte read of it; the row exponent is split instead, omega^r = HI[r >> s] * LO[r & (2^s - 1)] with s = ceil(k / 2), and DELTA^c comes
+// from a third table of n_perm_columns entries: 2^s + 2^(k-s) + m elements (48 KiB + 32 m bytes at k = 19) that every workgroup re-reads, two products per cell.
+// The tables are built on the host with the same Field routines and uploaded once per call.  (chosen by construction, not measured against the gather.)
+namespace {
+constexpr uint32_t KG_T = 256;
+
+// Every entry in range, every cell the image of exactly one cell.  status[0]: 0, or 2^32 - 1 - e for the FIRST cell e = j * 2^k + i whose entry is out of range (such an
+// entry is not used); status[1]: the cells whose image another cell had marked already.  seen: one bit per cell, zeroed by the caller.  (m << k < 2^32: the caller.)
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mapping_check_kernel(const uint32_t* map_c, const uint32_t* map_r, uint32_t m, uint32_t k, uint32_t* seen, uint32_t* status) {
+    const uint64_t cells = (uint64_t)m << k, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < cells; e += stride) {
+        const uint32_t c = map_c[e], r = map_r[e];
+        if (c >= m || r >= (1u << k)) { atomicMax(&status[0], 0xffffffffu - (uint32_t)e); continue; }
+        const uint32_t t = (c << k) | r, bit = 1u << (t & 31u);
+        if (atomicOr(&seen[t >> 5], bit) & bit) atomicAdd(&status[1], 1u);
+    }
+}
+// sigma[e >> k][e & (2^k - 1)] = dpow[map_c[e]] * hi[map_r[e] >> s] * lo[map_r[e] & (2^s - 1)] over a mapping mapping_check_kernel has passed
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) sigma_from_mapping_kernel(const uint32_t* map_c, const uint32_t* map_r, uint32_t m, uint32_t k, uint32_t s, const void* lo, const void* hi,
+                                                               const void* dpow, void* const* sigma) {
+    const uint64_t cells = (uint64_t)m << k, stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lo_mask = (1u << s) - 1u, row_mask = (1u << k) - 1u;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < cells; e += stride) {
+        const uint32_t c = map_c[e], r = map_r[e];
+        const u256 w = Fr::mul(load_u256(hi, r >> s), load_u256(lo, r & lo_mask));
+        store_u256(sigma[e >> k], (uint32_t)e & row_mask, Fr::mul(w, load_u256(dpow, c)));
+    }
+}
+
+// mapping planes (HOST) -> the m sigma columns (`sigma`: HOST array of DEVICE columns, 2^k x 32 B each); the mapping is checked first and nothing is written for a bad one
+int keygen_sigma(zk_ctx* ctx, const uint32_t* map_c, const uint32_t* map_r, uint32_t m, uint32_t k, void* const* sigma) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ZK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t cells = (size_t)m << k;
+    const uint32_t s = (k + 1) / 2, n_lo = 1u << s, n_hi = 1u << (k - s);
+    std::vector<u256> tab((size_t)n_lo + n_hi + m);
+    {
+        const uint64_t dl[4] = BN254_FR_DELTA_M;
+        u256 delta, w = domain_omega(k), ws = w;
+        memcpy(delta.v, dl, 32);
+        for (uint32_t i = 0; i < s; i++) ws = Fr::sqr(ws);             // omega^(2^s)
+        u256 acc = Fr::one();
+        for (uint32_t i = 0; i < n_lo; i++) { tab[i] = acc; acc = Fr::mul(acc, w); }
+        acc = Fr::one();
+        for (uint32_t i = 0; i < n_hi; i++) { tab[n_lo + i] = acc; acc = Fr::mul(acc, ws); }
+        acc = Fr::one();
+        for (uint32_t i = 0; i < m; i++) { tab[(size_t)n_lo + n_hi + i] = acc; acc = Fr::mul(acc, delta); }
+    }
+    const size_t seen_bytes = (cells + 31) / 32 * 4;
+    DevTmp d_mc, d_mr, d_seen, d_status, d_tab, d_out;
+    ZK_HIP(hipMalloc(&d_mc.p, cells * 4));
+    ZK_HIP(hipMalloc(&d_mr.p, cells * 4));
+    ZK_HIP(hipMalloc(&d_seen.p, seen_bytes));
+    ZK_HIP(hipMalloc(&d_status.p, 8));
+    ZK_HIP(hipMalloc(&d_tab.p, tab.size() * 32));
+    ZK_HIP(hipMalloc(&d_out.p, (size_t)m * sizeof(void*)));
+    ZK_HIP(hipMemcpyAsync(d_mc.p, map_c, cells * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_mr.p, map_r, cells * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 32, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_out.p, sigma, (size_t)m * sizeof(void*), hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemsetAsync(d_seen.p, 0, seen_bytes, st));
+    ZK_HIP(hipMemsetAsync(d_status.p, 0, 8, st));
+    const size_t want = (cells + KG_T - 1) / KG_T, cap = ctx->tune.keygen_wgs > 0 ? (size_t)ctx->tune.keygen_wgs : 1;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    uint32_t status[2] = {0, 0};
+    {
+        EvTimer t(ctx, "keygen_mapping_check");
+        ZK_LAUNCH(mapping_check_kernel, grid, KG_T, 0, st, (const uint32_t*)d_mc.p, (const uint32_t*)d_mr.p, m, k, (uint32_t*)d_seen.p, (uint32_t*)d_status.p);
+        ZK_CHECK_LAUNCH();
+        t.stop();
+        ZK_HIP(hipMemcpyAsync(status, d_status.p, 8, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        t.resolve();
+    }
+    if (status[0]) {
+        const uint32_t e = 0xffffffffu - status[0];
+        return ctx->fail(ZK_ERR_ARG, "zk_plonk_keygen_vk: the copy mapping sends cell (column %u, row %u) to (column %u, row %u), outside %u columns of 2^%u rows",
+                         e >> k, e & ((1u << k) - 1u), map_c[e], map_r[e], m, k);
+    }
+    if (status[1])
+        return ctx->fail(ZK_ERR_ARG, "zk_plonk_keygen_vk: the copy mapping is not a permutation of the cells: %u cells have an image that another cell has too", status[1]);
+    EvTimer t(ctx, "keygen_sigma");
+    ZK_LAUNCH(sigma_from_mapping_kernel, grid, KG_T, 0, st, (const uint32_t*)d_mc.p, (const uint32_t*)d_mr.p, m, k, s, (const void*)d_tab.p,
+              (const void*)((const char*)d_tab.p + (size_t)n_lo * 32), (const void*)((const char*)d_tab.p + ((size_t)n_lo + n_hi) * 32), (void* const*)d_out.p);
+    ZK_CHECK_LAUNCH();
+    t.stop();
+    ZK_HIP(hipStreamSynchronize(st));
+    t.resolve();
+    return ZK_OK;
+}
+
+// Keygen runs on one GPU with the whole table: `handle` must be a registered table of exactly 2^k points (params.g_lagrange) or, with at_least, of 2^k or more
+// (params.g).  A rank's slice of a sharded SRS holds fewer and is refused.
+int kg_whole_table(zk_ctx* ctx, const char* fn, const char* what, uint64_t handle, uint32_t k, bool at_least) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto it = ctx->bases.find(handle);
+    if (it == ctx->bases.end()) return ctx->fail(ZK_ERR_ARG, "%s: %s = %llu is not a registered table", fn, what, (unsigned long long)handle);
+    const size_t n = (size_t)1 << k, have = it->second.n;
+    if (have < n || (!at_least && have != n))
+        return ctx->fail(ZK_ERR_ARG, "%s: %s holds %zu points, keygen at k = %u needs the whole table of 2^%u (a slice of a sharded SRS is refused)", fn, what, have, k, k);
+    return ZK_OK;
+}
+
+struct KgHandle {
+    std::shared_ptr<KgCols> cols;
+    uint32_t k = 0;
+    std::vector<const void*> fixed, sigma;                            // DEVICE, Lagrange
+};
+std::map<std::pair<zk_ctx*, uint64_t>, KgHandle> g_kg_handles;       // (g_pk_mu; handle numbers are g_pk_next's)
+}  // namespace
+
+extern "C" int zk_plonk_keygen_vk(zk_ctx* ctx, const zk_plonk_keygen_desc* d, uint64_t srs_g_lagrange, void* fixed_commitments, void* permutation_commitments,
+                                  uint64_t* kg) ZK_ABI_TRY {
+    if (!ctx || !d || !kg) return ZK_ERR_ARG;
+    if (d->struct_size != sizeof(zk_plonk_keygen_desc))
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_vk: zk_plonk_keygen_desc.struct_size %u, expected %zu (ABI version %u)", d->struct_size, sizeof(zk_plonk_keygen_desc), ZK_ABI_VERSION);
+    const uint32_t k = d->k, F = d->n_fixed, M = d->n_perm_columns;
+    if (k < 1 || k > 27) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_vk: k = %u (1 .. 27)", k);
+    if ((F && (!d->fixed_values || !fixed_commitments)) || (M && (!d->perm_map_column || !d->perm_map_row || !permutation_commitments)))
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_vk: null column / mapping / output array");
+    for (uint32_t i = 0; i < F; i++) if (!d->fixed_values[i]) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_vk: fixed column %u is NULL", i);
+    if (((uint64_t)M << k) >= (1ull << 32)) return pk_fail(ctx, ZK_ERR_LIMIT, "zk_plonk_keygen_vk: %u permutation columns of 2^%u rows: 2^32 mapping cells or more", M, k);
+    PK(kg_whole_table(ctx, "zk_plonk_keygen_vk", "srs_g_lagrange", srs_g_lagrange, k, false));
+    const size_t n = (size_t)1 << k, col_bytes = n * 32;
+    KgHandle h;
+    h.k = k;
+    h.cols = std::make_shared<KgCols>();                              // (every way out but the last frees what was allocated so far)
+    h.cols->device = ctx->device;
+    auto alloc = [&]() -> void* {
+        h.cols->owned.reserve(h.cols->owned.size() + 1);
+        void* p = nullptr;
+        if (zk_dev_alloc(ctx, col_bytes, &p) != ZK_OK) return nullptr;
+        h.cols->owned.push_back(p);
+        return p;
+    };
+    std::vector<void*> up, sig;
+    for (uint32_t i = 0; i < F; i++) {
+        if (d->values_on_device) { h.fixed.push_back(d->fixed_values[i]); continue; }
+        void* p = alloc();
+        if (!p) return ZK_ERR_HIP;
+        up.push_back(p); h.fixed.push_back(p);
+    }
+    if (!up.empty()) PK(zk_dev_upload_batch(ctx, up.data(), d->fixed_values, up.size(), col_bytes));
+    for (uint32_t j = 0; j < M; j++) {
+        void* p = alloc();
+        if (!p) return ZK_ERR_HIP;
+        sig.push_back(p); h.sigma.push_back(p);
+    }
+    if (M) PK(keygen_sigma(ctx, d->perm_map_column, d->perm_map_row, M, k, sig.data()));
+    std::vector<const void*> all(h.fixed);
+    all.insert(all.end(), h.sigma.begin(), h.sigma.end());
+    std::vector<unsigned char> points(all.size() * 96 + 1);
+    if (!all.empty()) PK(zk_msm_batch_dev(ctx, srs_g_lagrange, all.data(), all.size(), n, points.data()));
+    if (F) memcpy(fixed_commitments, points.data(), (size_t)F * 96);
+    if (M) memcpy(permutation_commitments, points.data() + (size_t)F * 96, (size_t)M * 96);
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    g_kg_handles[{ctx, g_pk_next}] = std::move(h);
+    *kg = g_pk_next++;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_keygen_columns(zk_ctx* ctx, uint64_t kg, const void** fixed_dev, const void** sigma_dev) ZK_ABI_TRY {
+    if (!ctx) return ZK_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_kg_handles.find({ctx, kg});
+    if (it == g_kg_handles.end()) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_columns: unknown keygen handle %llu", (unsigned long long)kg);
+    const KgHandle& h = it->second;
+    if ((!h.fixed.empty() && !fixed_dev) || (!h.sigma.empty() && !sigma_dev)) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_columns: null output array");
+    for (size_t i = 0; i < h.fixed.size(); i++) fixed_dev[i] = h.fixed[i];
+    for (size_t j = 0; j < h.sigma.size(); j++) sigma_dev[j] = h.sigma[j];
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_keygen_pk(zk_ctx* ctx, uint64_t kg, const zk_plonk_pk_host* host, const zk_plonk_phases* phases, uint64_t srs_g, uint64_t srs_g_lagrange,
+                                  uint64_t* pk) ZK_ABI_TRY {
+    if (!ctx || !host || !pk) return ZK_ERR_ARG;
+    if (host->struct_size != sizeof(zk_plonk_pk_host))
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_pk: zk_plonk_pk_host.struct_size %u, expected %zu (ABI version %u)", host->struct_size, sizeof(zk_plonk_pk_host), ZK_ABI_VERSION);
+    if (host->fixed_values || host->sigma_values)
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_pk: host->fixed_values / sigma_values must be NULL: the key is built on the keygen handle's columns");
+    if (host->shard_world > 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_pk: shard_world %u: keygen runs on one GPU with the whole table", host->shard_world);
+    KgHandle h;                                                       // a copy: the columns stay alive through the build whatever another thread releases meanwhile
+    {
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        auto it = g_kg_handles.find({ctx, kg});
+        if (it == g_kg_handles.end()) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_pk: unknown keygen handle %llu", (unsigned long long)kg);
+        h = it->second;
+    }
+    if (host->k != h.k || host->n_fixed != h.fixed.size() || host->n_perm_columns != h.sigma.size())
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_keygen_pk: host describes k = %u with %u fixed and %u permutation columns, the keygen handle holds k = %u with %zu and %zu",
+                       host->k, host->n_fixed, host->n_perm_columns, h.k, h.fixed.size(), h.sigma.size());
+    PK(kg_whole_table(ctx, "zk_plonk_keygen_pk", "srs_g", srs_g, h.k, true));
+    PK(kg_whole_table(ctx, "zk_plonk_keygen_pk", "srs_g_lagrange", srs_g_lagrange, h.k, false));
+    zk_plonk_pk_host on_handle = *host;
+    h.fixed.push_back(nullptr); h.sigma.push_back(nullptr);           // (.data() of an empty vector may be null)
+    on_handle.fixed_values = h.fixed.data(); on_handle.sigma_values = h.sigma.data(); on_handle.values_on_device = 1;
+    return pk_build(ctx, &on_handle, phases, srs_g, srs_g_lagrange, pk, h.cols);
+} ZK_ABI_CATCH(ctx)
+
+extern "C" int zk_plonk_keygen_release(zk_ctx* ctx, uint64_t kg) ZK_ABI_TRY {
+    if (!ctx) return ZK_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_kg_handles.find({ctx, kg});
+    if (it == g_kg_handles.end()) return ZK_ERR_ARG;
+    g_kg_handles.erase(it);
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+
 // zk_ctx_destroy (capi.hip): the keys this context still holds go with it (before its programs are released)
 void zk_internal_plonk_ctx_destroyed(zk_ctx* ctx) {
     std::lock_guard<std::mutex> lk(g_pk_mu);
@@ -339,4 +566,5 @@ void zk_internal_plonk_ctx_destroyed(zk_ctx* ctx) {
         if (it->first.first == ctx) { if (it->second->in_use) it->second->released = true; else pk_drop(ctx, it->second); it = g_pk_handles.erase(it); }
         else ++it;
     }
+    for (auto it = g_kg_handles.begin(); it != g_kg_handles.end();) it = it->first.first == ctx ? g_kg_handles.erase(it) : std::next(it);
 }

@@ -3,6 +3,8 @@ circuits/src/sgx_dcap_verifier.rs:803,807,814-822), as a host-side mirror over t
 
     ConstraintSystem, Assembly, Expression (Advice / Fixed / Instance / Constant …)      circuit description
     keygen(params, cs, fixed_columns, assembly) -> ProvingKey                            keygen_vk + keygen_pk
+    keygen_vk_native(params, cs, fixed_columns, assembly) -> (VerifyingKey, NativeKeygen) keygen_vk in the library: sigma from the copy mapping on the GPU (zk_plonk_keygen_vk)
+    NativeKey.from_keygen(params, kg, vk)                                                keygen_pk on those resident columns (zk_plonk_keygen_pk)
     create_proof(params, pk, advice_columns, instances, rng, transcript)                 plonk::create_proof + ProverSHPLONK (Python twin; multi-GPU driver)
     NativeProver(params, pk).create_proof(advice_columns, instances, rng) -> bytes       the same per-proof path in C++ (zk_plonk_create_proof)
     PhasedProver(params, pk).create_proof(advices, instances, rng, next_phase) -> bytes  advice in phases with halo2's Challenge API (zk_plonk_prove_phased)
@@ -15,7 +17,7 @@ pure-Python verifier as the acceptance check, outside this package.
 from .circuit import ADVICE, FIXED, INSTANCE, Assembly, ConstraintSystem, LookupArgument  # noqa: F401
 from .dev import MockProver, NativeMockProver, VerifyFailure  # noqa: F401
 from .expression import Advice, Challenge, Constant, Expression, Fixed, Instance  # noqa: F401
-from .keygen import NativeKey, ProvingKey, VerifyingKey, compile_program, keygen  # noqa: F401
+from .keygen import KeyView, NativeKey, NativeKeygen, ProvingKey, VerifyingKey, compile_program, keygen, keygen_vk_native  # noqa: F401
 from .prover import create_proof  # noqa: F401
 from .native import NativeProver, PhasedProver, create_proof_native, last_challenges  # noqa: F401
 from .shplonk import ProverSHPLONK  # noqa: F401

@@ -126,8 +126,71 @@ def compressor_program(cs: ConstraintSystem, k: int, exprs) -> ev.Program:
     return ev.expression_program(k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, cs.num_challenges, gb.graph)
 
 
-def _compressor(cs: ConstraintSystem, k: int, exprs, be: Backend) -> ev.Evaluator:
-    return ev.Evaluator(compressor_program(cs, k, exprs), backend=be)
+def _extended_k(cs: ConstraintSystem, k: int) -> int:
+    """EvaluationDomain::new(cs.degree(), k): the smallest extended domain that holds a quotient of degree (cs.degree() - 1) * 2^k"""
+    ek = k
+    while (1 << ek) < (1 << k) * (cs.degree() - 1):
+        ek += 1
+    return ek
+
+
+def _programs(cs: ConstraintSystem, k: int, extended_k: int):
+    """every ZKQ1 program of a key -> (Evaluator program, per lookup its input program, per lookup its table program): one place for keygen() and
+    NativeKey.from_keygen, whose proofs are equal byte for byte only while they compile the same programs"""
+    return (compile_program(cs, k, extended_k), [compressor_program(cs, k, lk.input_expressions) for lk in cs.lookups],
+            [compressor_program(cs, k, lk.table_expressions) for lk in cs.lookups])
+
+
+@dataclass
+class KeyView:
+    """what a key built by NativeKey.from_keygen has in a ProvingKey's place: the verifying key and the backend (the columns are the library's)"""
+    vk: VerifyingKey
+    backend: Backend
+
+
+class NativeKeygen:
+    """The handle of zk_plonk_keygen_vk: the fixed and sigma columns in Lagrange form, resident in HBM, shared with every key built from it (NativeKey.from_keygen)."""
+
+    def __init__(self, backend: Backend, handle: int, k: int, n_fixed: int, n_perm_columns: int):
+        self.backend, self.handle, self.k, self.n_fixed, self.n_perm_columns = backend, handle, k, n_fixed, n_perm_columns
+
+    def columns(self):
+        """(fixed, sigma): device pointers of the Lagrange columns, valid until release()"""
+        return self.backend.plonk_keygen_columns(self.handle, self.n_fixed, self.n_perm_columns)
+
+    def download(self):
+        """(fixed, sigma) as (2^k, 4) uint64 Montgomery arrays"""
+        import ctypes as C
+        be, n = self.backend, 1 << self.k
+
+        def get(ptr):
+            out = np.empty((n, 4), dtype=np.uint64)
+            be._ck(be.lib.zk_dev_download(be.ctx, out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(out.nbytes)))
+            return out
+        fx, sg = self.columns()
+        return [get(p) for p in fx], [get(p) for p in sg]
+
+    def release(self):
+        if self.handle:
+            self.backend.plonk_keygen_release(self.handle)
+            self.handle = 0
+
+
+def keygen_vk_native(params: ParamsKZG, cs: ConstraintSystem, fixed_columns, assembly: Optional[Assembly] = None):
+    """keygen_vk through zk_plonk_keygen_vk -> (VerifyingKey, NativeKeygen): the sigma columns are built on the device from the copy mapping (Assembly.map_c / map_r;
+    None = the identity mapping) and every fixed and sigma column is committed in one batch — no identity column is downloaded, no sigma column uploaded.  The
+    VerifyingKey equals keygen()'s (same commitments, same transcript_repr), so both routes prove the same bytes; NativeKey.from_keygen builds the proving key."""
+    be, k, n = params.backend, params.k, params.n
+    assert params.world == 1, "keygen runs on one GPU with the whole table"
+    assert len(fixed_columns) == cs.num_fixed_columns
+    assert n > cs.blinding_factors() + 1 + 1, "circuit does not fit: not enough usable rows"
+    m = len(cs.permutation_columns)
+    asm = (assembly or Assembly(cs, k)) if m else None
+    fc, pc, handle = be.plonk_keygen_vk(k, [_as_mont(c, n) for c in fixed_columns], asm.map_c if m else None, asm.map_r if m else None, params.g_lagrange.handle)
+    fixed_commitments = [g1_affine_ints(r) for r in fc]
+    permutation_commitments = [g1_affine_ints(r) for r in pc]
+    vk = VerifyingKey(k, cs, fixed_commitments, permutation_commitments, _transcript_repr(k, cs, fixed_commitments, permutation_commitments))
+    return vk, NativeKeygen(be, handle, k, cs.num_fixed_columns, m)
 
 
 class NativeKey:
@@ -136,10 +199,24 @@ class NativeKey:
 
     def __init__(self, params: ParamsKZG, pk: "ProvingKey", transcript: int = 0):
         import ctypes as C
-        from .._lib import PlonkPhases, _dptr
-        from .native import PkHost
-        be, cs = pk.backend, pk.vk.cs
+        from .._lib import _dptr
+        be = pk.backend
         assert params.world == 1, "one proof over several GPUs is single-phase (zk_plonk_pk_build_phased refuses shard_world > 1)"
+        h, ph, keep, ptrs = self._host(params, pk.vk, pk.program, [a.program for a, _ in pk.lookup_compressors], [b.program for _, b in pk.lookup_compressors], transcript)
+        h.fixed_values, h.sigma_values, h.values_on_device = ptrs([_dptr(d) for d in pk.fixed_values]), ptrs([_dptr(d) for d in pk.sigma_values]), 1
+        self.host, self.phases, self._keep = h, ph, keep               # (kept: tests rebuild with altered copies)
+        self.backend, self.pk = be, pk
+        out = C.c_uint64()
+        be._ck(be.lib.zk_plonk_pk_build_phased(be.ctx, C.byref(h), C.byref(ph), C.c_uint64(params.g.handle), C.c_uint64(params.g_lagrange.handle), C.byref(out)))
+        self.handle = out.value
+
+    @staticmethod
+    def _host(params: ParamsKZG, vk: "VerifyingKey", program, input_programs, table_programs, transcript: int):
+        """zk_plonk_pk_host and zk_plonk_phases of a circuit, the column pointers left NULL -> (host, phases, what they point into, ptrs())"""
+        import ctypes as C
+        from .._lib import PlonkPhases
+        from .native import PkHost
+        cs = vk.cs
         keep = []
 
         def u32(vals):
@@ -170,14 +247,13 @@ class NativeKey:
         aq, fq = cs.advice_queries(), cs.fixed_queries()
         h.advice_queries, h.n_advice_queries = u32([v for c, r in aq for v in (c, r)]), len(aq)
         h.fixed_queries, h.n_fixed_queries = u32([v for c, r in fq for v in (c, r)]), len(fq)
-        ev_blob = (C.c_char * len(pk.program.to_blob())).from_buffer_copy(pk.program.to_blob())
+        ev_blob = (C.c_char * len(program.to_blob())).from_buffer_copy(program.to_blob())
         keep.append(ev_blob)
         h.evaluator_zkq1, h.evaluator_zkq1_len = C.addressof(ev_blob), len(ev_blob)
-        h.lookup_input_zkq1, h.lookup_input_zkq1_len = blobs([a.program for a, _ in pk.lookup_compressors])
-        h.lookup_table_zkq1, h.lookup_table_zkq1_len = blobs([b.program for _, b in pk.lookup_compressors])
+        h.lookup_input_zkq1, h.lookup_input_zkq1_len = blobs(input_programs)
+        h.lookup_table_zkq1, h.lookup_table_zkq1_len = blobs(table_programs)
         h.lookup_table_key = u32(key_ids)
-        h.fixed_values, h.sigma_values, h.values_on_device = ptrs([_dptr(d) for d in pk.fixed_values]), ptrs([_dptr(d) for d in pk.sigma_values]), 1
-        repr_bytes = np.frombuffer(int(pk.vk.transcript_repr).to_bytes(32, "little"), dtype=np.uint8).copy()
+        repr_bytes = np.frombuffer(int(vk.transcript_repr).to_bytes(32, "little"), dtype=np.uint8).copy()
         keep.append(repr_bytes)
         h.transcript_repr, h.transcript, h.draw_schedule = repr_bytes.ctypes.data, transcript, 1
         ph = PlonkPhases()
@@ -187,11 +263,19 @@ class NativeKey:
         keep += [ap, cp]
         ph.n_advice, ph.advice_phase = len(ap), ap.ctypes.data if ap.size else None
         ph.n_challenges, ph.challenge_phase = len(cp), cp.ctypes.data if cp.size else None
-        self.host, self.phases, self._keep = h, ph, keep               # (kept: tests rebuild with altered copies)
-        self.backend, self.pk = be, pk
-        out = C.c_uint64()
-        be._ck(be.lib.zk_plonk_pk_build_phased(be.ctx, C.byref(h), C.byref(ph), C.c_uint64(params.g.handle), C.c_uint64(params.g_lagrange.handle), C.byref(out)))
-        self.handle = out.value
+        return h, ph, keep, ptrs
+
+    @classmethod
+    def from_keygen(cls, params: ParamsKZG, kg: "NativeKeygen", vk: "VerifyingKey", transcript: int = 0) -> "NativeKey":
+        """keygen_pk on the columns keygen_vk_native left in HBM (zk_plonk_keygen_pk): no column crosses the link again and sigma is not recomputed.  The key shares
+        the columns with `kg`: either may be released first.  `.pk` is a KeyView (vk + backend), which is what plonk.PhasedProver(params, key.pk, key=key) reads."""
+        assert params.world == 1, "keygen runs on one GPU with the whole table (zk_plonk_keygen_pk refuses shard_world > 1)"
+        program, input_programs, table_programs = _programs(vk.cs, params.k, _extended_k(vk.cs, params.k))
+        self = cls.__new__(cls)
+        self.host, self.phases, self._keep, _ = cls._host(params, vk, program, input_programs, table_programs, transcript)
+        self.backend, self.pk = kg.backend, KeyView(vk, kg.backend)
+        self.handle = kg.backend.plonk_keygen_pk(kg.handle, self.host, self.phases, params.g.handle, params.g_lagrange.handle)
+        return self
 
     def shared_with(self, backend, params: ParamsKZG) -> "NativeKey":
         """the same key for another context of the same GPU (zk_plonk_pk_share); `params` is that context's SRS"""
@@ -208,6 +292,16 @@ class NativeKey:
         if self.handle:
             self.backend._ck(self.backend.lib.zk_plonk_pk_release(self.backend.ctx, C.c_uint64(self.handle)))
             self.handle = 0
+
+
+def _transcript_repr(k: int, cs: ConstraintSystem, fixed_commitments, permutation_commitments) -> int:
+    """vk.transcript_repr of this package (module docstring): one hash for keygen() and keygen_vk_native(), so that both routes prove the same bytes"""
+    h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
+    h.update(repr((k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, len(cs.gates), len(cs.lookups),
+                   cs.permutation_columns, cs.degree(), fixed_commitments, permutation_commitments)).encode())
+    if cs.is_phased():                                                   # (halo2's pinned vk renders advice_column_phase / challenge_phase too; single-phase circuits keep their bytes)
+        h.update(repr(("phases", cs._advice_phases(), list(cs.challenge_phase))).encode())
+    return int.from_bytes(h.digest(), "little") % R_MOD
 
 
 def _as_mont(col, n) -> np.ndarray:
@@ -256,12 +350,7 @@ def keygen(params: ParamsKZG, cs: ConstraintSystem, fixed_columns, assembly: Opt
     pc = params.commit_columns("g_lagrange", sigma_values)
     fixed_commitments = [g1_affine_ints(r) for r in fc]
     permutation_commitments = [g1_affine_ints(r) for r in pc]
-    h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
-    h.update(repr((k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, len(cs.gates), len(cs.lookups),
-                   cs.permutation_columns, cs.degree(), fixed_commitments, permutation_commitments)).encode())
-    if cs.is_phased():                                                   # (halo2's pinned vk renders advice_column_phase / challenge_phase too; single-phase circuits keep their bytes)
-        h.update(repr(("phases", cs._advice_phases(), list(cs.challenge_phase))).encode())
-    vk = VerifyingKey(k, cs, fixed_commitments, permutation_commitments, int.from_bytes(h.digest(), "little") % R_MOD)
+    vk = VerifyingKey(k, cs, fixed_commitments, permutation_commitments, _transcript_repr(k, cs, fixed_commitments, permutation_commitments))
 
     # keygen_pk: polys and extended cosets (when the quotient is sharded: only this rank's cosets, 2^k values each)
     by_cosets = params.by_cosets()
@@ -309,8 +398,9 @@ def keygen(params: ParamsKZG, cs: ConstraintSystem, fixed_columns, assembly: Opt
     if by_cosets:
         lcosets = [None, None, None]
 
-    program = compile_program(cs, k, ek)
+    assert ek == _extended_k(cs, k)
+    program, input_programs, table_programs = _programs(cs, k, ek)
     evaluator = ev.Evaluator(program, backend=be)
-    comps = [(_compressor(cs, k, lk.input_expressions, be), _compressor(cs, k, lk.table_expressions, be)) for lk in cs.lookups]
+    comps = [(ev.Evaluator(a, backend=be), ev.Evaluator(b, backend=be)) for a, b in zip(input_programs, table_programs)]
     return ProvingKey(vk, dom, be, fixed_values, fixed_polys, fixed_cosets, sigma_values, sigma_polys, sigma_cosets,
                       lcosets[0], lcosets[1], lcosets[2], evaluator, program, comps, coset_parts, False, pieces_from_cosets=pieces_from_cosets)
