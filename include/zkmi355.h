@@ -52,10 +52,11 @@ typedef struct zk_ctx zk_ctx;
  * call instead of handing the library bytes past the end of its object.  Fields are only ever APPENDED, and each append bumps ZK_ABI_VERSION; a binding
  * asserts at start-up that zk_abi_version() is the ZK_ABI_VERSION it was written against and that zk_abi_struct_size(name) equals its own size of every
  * struct it declares (shim/halo2_proofs_mi355x/src/mi355x.rs does; tests/test_shim_abi.py diffs the declarations field by field). */
-#define ZK_ABI_VERSION 7u
+#define ZK_ABI_VERSION 8u
 uint32_t zk_abi_version(void);
-/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure", "zk_plonk_phases", "zk_plonk_keygen_desc") in this build of the library; 0 for an
- * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify), version 7 the keygen descriptor (zk_plonk_keygen_vk). */
+/* sizeof the named struct ("zk_quotient_args", "zk_plonk_pk_desc", "zk_plonk_pk_host", "zk_mock_desc", "zk_mock_failure", "zk_plonk_phases", "zk_plonk_keygen_desc", "zk_mock_witness", "zk_mock_info") in this build of the library; 0 for an
+ * unknown name.  Version 5 added the MockProver structs (zk_mock_prover_verify), version 7 the keygen descriptor (zk_plonk_keygen_vk), version 8 the MockProver
+ * session (zk_mock_prover_open). */
 uint32_t zk_abi_struct_size(const char* struct_name);
 #define ZK_STRUCT_INIT(s) do { memset(&(s), 0, sizeof(s)); (s).struct_size = (uint32_t)sizeof(s); } while (0)   /* needs <string.h> */
 
@@ -552,6 +553,53 @@ int zk_mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* desc, zk_mock_failure
  * every blob must declare exactly n_challenges challenges (ZK_ERR_ARG otherwise); n_challenges = 0 takes what zk_mock_prover_verify takes. */
 int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const void* challenges, uint32_t n_challenges, zk_mock_failure* out, size_t cap,
                                  uint64_t counts[3], size_t* n_written);
+
+/* ---- MockProver session: the circuit stays resident, any number of witnesses is checked against it ------------------------------------------------------ *
+ * zk_mock_prover_verify pays per call for work that depends on the circuit alone: the upload of the copy mapping (8 B per cell of every permutation column), the
+ * compilation of the gate and lookup programs, the compression and sort of every lookup table, a hipMalloc / hipFree per temporary.  A caller that checks many
+ * witnesses of ONE circuit (one key, many proofs: each witness is checked before it is proven) opens a session once and pays per witness for the kernels only.
+ * zk_mock_prover_open takes the zk_mock_desc of zk_mock_prover_verify; advice_values, instances and instance_lens are ignored and may be NULL.  It validates as
+ * zk_mock_prover_verify does, with the same codes (a copy-mapping entry out of range: ZK_ERR_ARG), uploads the fixed columns once (values_on_device: borrowed, they
+ * must outlive the handle), reduces the copy mapping on the device to its COPY EDGES - the cells whose image is not the cell itself, one packed pair of u32
+ * (cell, image), both = column * 2^k + row, in cell order - and frees the planes, compiles the gate program and every distinct lookup blob once (byte-equal blobs
+ * share one program), and sorts once every lookup table whose program reads fixed columns and constants only ("resident": no advice, no instance, no challenge; a
+ * program the reader cannot classify is treated as per-check, which is always correct).  Nothing of `desc` is referenced after the call; every workspace of a check
+ * is allocated here.  On an error *mp is left untouched and nothing stays allocated.
+ * zk_mock_prover_check returns for one witness exactly what zk_mock_prover_verify(_phased) returns for the same circuit and witness: the same records in the
+ * same order, exact counts, the first `cap` records.  Copies: one thread per edge (a coalesced 8-byte read and two gathers, compared fully reduced); gates: as
+ * zk_mock_prover_verify, r drawn per call; lookups: a per-check table is compressed with a theta drawn per call and sorted once per check (byte-equal blobs once), a
+ * resident table was compressed with a theta drawn at zk_mock_prover_open, and every lookup's input is compressed with ITS TABLE's theta - so two lookups of one call
+ * may use different thetas.  In the steady state a check allocates and frees no device memory (the record buffers grow with the number of failures and are kept;
+ * host columns are staged in buffers allocated by the first such check).
+ * Soundness of the resident theta: it is never returned, and the bound (m - 1) / |Fr| per missing tuple of m expressions holds for every witness chosen independently
+ * of it.  What a caller learns from earlier checks is only whether a collision occurred - an event of that same probability - so a caller who adapts witnesses to
+ * earlier answers gains nothing until a collision has already happened.
+ * n_challenges must equal what every blob declares (0: the single-phase case; then challenges may be NULL).
+ * ZK_ERR_ARG from zk_mock_prover_check: a wrong struct_size, a NULL advice column, a non-canonical instance, a wrong challenge count, a handle that is closed or
+ * belongs to another context.  After any error the handle stays usable.
+ * Handles are per context: zk_ctx_destroy releases those still open; zk_plonk_trim does not touch them.  Timing labels (zk_timing_get): "mock_open",
+ * "mock_copy_edges", and zk_mock_prover_verify's "mock_gates", "mock_gate_rows", "mock_lookups".  Tunable "mock_edge_wgs": the workgroups (of 256 edges per step) the
+ * edge kernels launch at most, 2048 by default; the edges beyond are a grid stride. */
+typedef struct zk_mock_witness zk_mock_witness;
+typedef struct zk_mock_info zk_mock_info;
+struct zk_mock_witness {
+    uint32_t struct_size;                       /* sizeof(zk_mock_witness) of the caller (ABI versioning) */
+    const void* const* advice_values;           /* n_advice columns, 2^k x 32 B Montgomery; HOST, or DEVICE with values_on_device */
+    const void* const* instances; const uint32_t* instance_lens;   /* as zk_mock_desc */
+    uint32_t values_on_device;                  /* of advice_values (the fixed columns follow zk_mock_desc.values_on_device at zk_mock_prover_open) */
+    const void* challenges; uint32_t n_challenges;                 /* HOST, n_challenges x 32 B Montgomery, as zk_mock_prover_verify_phased */
+};
+struct zk_mock_info {
+    uint32_t struct_size;                       /* sizeof(zk_mock_info) of the caller (ABI versioning) */
+    uint32_t n_tables, n_resident_tables;       /* distinct lookup table blobs; those sorted once at zk_mock_prover_open */
+    uint32_t n_programs;                        /* compiled programs the handle holds (the gate program and one per distinct lookup blob) */
+    uint64_t n_edges, n_cells;                  /* copy edges kept; n_perm_columns x 2^k cells of the mapping */
+    uint64_t device_bytes;                      /* device memory the handle owns (borrowed columns not counted) */
+};
+int zk_mock_prover_open(zk_ctx* ctx, const zk_mock_desc* desc, uint64_t* mp);
+int zk_mock_prover_check(zk_ctx* ctx, uint64_t mp, const zk_mock_witness* w, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written);
+int zk_mock_prover_info(zk_ctx* ctx, uint64_t mp, zk_mock_info* info);
+int zk_mock_prover_close(zk_ctx* ctx, uint64_t mp);
 
 /* ---- keygen: halo2_proofs::plonk::{keygen_vk, keygen_pk} after synthesis (src/plonk/keygen.rs; reference call sites circuits/src/sgx_dcap_verifier.rs:803,807) --------- *
  * zk_plonk_keygen_vk: from the fixed columns as halo2 holds them after selector compression and the copy mapping of permutation::keygen::Assembly (two u32 planes,

@@ -17,7 +17,7 @@ pub struct ZkCtx {
 }
 
 /// ZK_ABI_VERSION of the include/zkmi355.h this file was written against
-pub const ZK_ABI_VERSION: u32 = 7;
+pub const ZK_ABI_VERSION: u32 = 8;
 
 /// field-for-field `zk_quotient_args`
 #[repr(C)]
@@ -133,6 +133,8 @@ pub fn gpu() -> Option<&'static Gpu> {
         assert_eq!(unsafe { zk_abi_struct_size(b"zk_plonk_pk_host\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::pk_desc::ZkPlonkPkHost>());
         assert_eq!(unsafe { zk_abi_struct_size(b"zk_plonk_phases\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::pk_desc::ZkPlonkPhases>());
         assert_eq!(unsafe { zk_abi_struct_size(b"zk_plonk_keygen_desc\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::keygen_native::ZkPlonkKeygenDesc>());
+        assert_eq!(unsafe { zk_abi_struct_size(b"zk_mock_witness\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::mock_session::ZkMockWitness>());
+        assert_eq!(unsafe { zk_abi_struct_size(b"zk_mock_info\0".as_ptr() as *const c_char) } as usize, std::mem::size_of::<crate::mock_session::ZkMockInfo>());
         let dev = std::env::var("HALO2_MI355X_DEVICE").ok().and_then(|s| s.parse().ok()).unwrap_or(0);
         let mut ctx = std::ptr::null_mut();
         if unsafe { zk_ctx_create(dev, &mut ctx) } != 0 {

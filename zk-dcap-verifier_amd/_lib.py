@@ -26,7 +26,7 @@ class ZkError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 7          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
+ABI_VERSION = 8          # ZK_ABI_VERSION of include/zkmi355.h this binding follows
 
 
 class QuotientArgs(C.Structure):
@@ -67,6 +67,18 @@ class KeygenDesc(C.Structure):
 PHASE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))     # zk_phase_fn
 
 
+class MockWitness(C.Structure):
+    """zk_mock_witness (zk_mock_prover_check)"""
+    _fields_ = [("struct_size", C.c_uint32), ("advice_values", C.c_void_p), ("instances", C.c_void_p), ("instance_lens", C.c_void_p),
+                ("values_on_device", C.c_uint32), ("challenges", C.c_void_p), ("n_challenges", C.c_uint32)]
+
+
+class MockInfo(C.Structure):
+    """zk_mock_info (zk_mock_prover_info)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_tables", C.c_uint32), ("n_resident_tables", C.c_uint32), ("n_programs", C.c_uint32),
+                ("n_edges", C.c_uint64), ("n_cells", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 class MockFailure(C.Structure):
     """zk_mock_failure: kind 0 gate / 1 lookup / 2 copy"""
     _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("other_column", C.c_uint32), ("other_row", C.c_uint32)]
@@ -88,7 +100,8 @@ def _load(path: str):
         raise RuntimeError(f"{path}: ABI version {lib.zk_abi_version()}, this binding is written against {ABI_VERSION} (rebuild: __graft_entry__.build())")
     if lib.zk_abi_struct_size(b"zk_quotient_args") != C.sizeof(QuotientArgs):
         raise RuntimeError(f"{path}: sizeof(zk_quotient_args) = {lib.zk_abi_struct_size(b'zk_quotient_args')}, the binding's QuotientArgs has {C.sizeof(QuotientArgs)}")
-    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure), (b"zk_plonk_phases", PlonkPhases), (b"zk_plonk_keygen_desc", KeygenDesc)):
+    for name, st in ((b"zk_mock_desc", MockDesc), (b"zk_mock_failure", MockFailure), (b"zk_plonk_phases", PlonkPhases), (b"zk_plonk_keygen_desc", KeygenDesc),
+                     (b"zk_mock_witness", MockWitness), (b"zk_mock_info", MockInfo)):
         if lib.zk_abi_struct_size(name) != C.sizeof(st):
             raise RuntimeError(f"{path}: sizeof({name.decode()}) = {lib.zk_abi_struct_size(name)}, the binding's {st.__name__} has {C.sizeof(st)}")
     return lib
@@ -505,14 +518,10 @@ class Backend:
                                             C.c_void_p(_dptr(out_dev))))
 
     # -- MockProver ------------------------------------------------------------------------------
-    def mock_prover_verify(self, *, k: int, blinding_factors: int, n_fixed: int, n_advice: int, n_instance: int, perm_columns, evaluator_blob: bytes,
-                           lookup_input_blobs, lookup_table_blobs, fixed, advice, instances, perm_map_column=None, perm_map_row=None, cap: int = 0,
-                           struct_size: int | None = None, challenges=None):
-        """zk_mock_prover_verify.  fixed / advice: (2^k, 4) uint64 Montgomery arrays (host) or device buffers (all of one kind; None = a NULL column);
-        instances: canonical ints per instance column; perm_map_column / perm_map_row: (n_perm_columns, 2^k) integer arrays (Assembly.map_c / map_r).
-        Returns ([(kind, index, row, other_column, other_row)] for the first `cap` failures, (gate, lookup, copy) counts)."""
-        keep = []
-
+    def _mock_desc(self, keep, *, k: int, blinding_factors: int, n_fixed: int, n_advice: int, n_instance: int, perm_columns, evaluator_blob: bytes,
+                   lookup_input_blobs, lookup_table_blobs, fixed, advice=None, instances=None, perm_map_column=None, perm_map_row=None,
+                   struct_size: int | None = None) -> MockDesc:
+        """zk_mock_desc of the arguments; `keep` receives every buffer the descriptor points into.  advice / instances None: NULL (zk_mock_prover_open)"""
         def arr(a, dtype):
             a = np.ascontiguousarray(np.asarray(a).astype(dtype, copy=False))
             keep.append(a)
@@ -522,7 +531,7 @@ class Backend:
             p = (C.c_void_p * max(1, len(vals)))(*vals)
             keep.append(p)
             return C.cast(p, C.c_void_p).value
-        cols = list(fixed) + list(advice)
+        cols = list(fixed) + list(advice or [])
         on_device = any(c is not None and not isinstance(c, np.ndarray) for c in cols)
         if on_device:
             col_ptr = lambda c: None if c is None else _dptr(c)
@@ -532,8 +541,6 @@ class Backend:
         bufs = [(C.c_char * max(1, len(b))).from_buffer_copy(b or b"\0") for b in blob_bufs]
         keep.extend(bufs)
         L = len(lookup_input_blobs)
-        inst = [np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in col) or bytes(32), dtype=np.uint8).copy() for col in instances]
-        keep.extend(inst)
         d = MockDesc()
         d.struct_size = C.sizeof(MockDesc) if struct_size is None else struct_size
         d.k, d.blinding_factors = k, blinding_factors
@@ -545,25 +552,94 @@ class Backend:
         d.lookup_table_zkq1 = ptrs([C.addressof(b) for b in bufs[1 + L:]])
         d.lookup_table_zkq1_len = arr([len(b) for b in lookup_table_blobs] or [0], np.uint64)
         d.fixed_values = ptrs([col_ptr(c) for c in fixed])
-        d.advice_values = ptrs([col_ptr(c) for c in advice])
-        d.instances = ptrs([a.ctypes.data for a in inst])
-        d.instance_lens = arr([len(col) for col in instances] or [0], np.uint32)
+        if advice is not None:
+            d.advice_values = ptrs([col_ptr(c) for c in advice])
+        if instances is not None:
+            inst = [np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in col) or bytes(32), dtype=np.uint8).copy() for col in instances]
+            keep.extend(inst)
+            d.instances = ptrs([a.ctypes.data for a in inst])
+            d.instance_lens = arr([len(col) for col in instances] or [0], np.uint32)
         if perm_columns:
             d.perm_map_column = arr(perm_map_column, np.uint32)
             d.perm_map_row = arr(perm_map_row, np.uint32)
         d.values_on_device = 1 if on_device else 0
+        return d
+
+    @staticmethod
+    def _mock_challenges(challenges):
+        """canonical ints -> Montgomery limbs (n_challenges x 32 B)"""
+        from .fields import fr_mont_array
+        return np.ascontiguousarray(fr_mont_array([int(c) for c in challenges]) if len(challenges) else np.zeros((1, 4), np.uint64))
+
+    def mock_prover_verify(self, *, cap: int = 0, challenges=None, **desc):
+        """zk_mock_prover_verify.  fixed / advice: (2^k, 4) uint64 Montgomery arrays (host) or device buffers (all of one kind; None = a NULL column);
+        instances: canonical ints per instance column; perm_map_column / perm_map_row: (n_perm_columns, 2^k) integer arrays (Assembly.map_c / map_r).
+        Returns ([(kind, index, row, other_column, other_row)] for the first `cap` failures, (gate, lookup, copy) counts)."""
+        keep = []
+        d = self._mock_desc(keep, **desc)
         out = (MockFailure * max(1, cap))()
         counts = (C.c_uint64 * 3)()
         written = C.c_size_t()
         if challenges is None:
             self._ck(self.lib.zk_mock_prover_verify(self.ctx, C.byref(d), out, C.c_size_t(cap), counts, C.byref(written)))
         else:                                                            # zk_mock_prover_verify_phased: canonical ints -> Montgomery limbs
-            from .fields import fr_mont_array
-            ch = np.ascontiguousarray(fr_mont_array([int(c) for c in challenges]) if len(challenges) else np.zeros((1, 4), np.uint64))
+            ch = self._mock_challenges(challenges)
             self._ck(self.lib.zk_mock_prover_verify_phased(self.ctx, C.byref(d), ch.ctypes.data_as(C.c_void_p), C.c_uint32(len(challenges)), out, C.c_size_t(cap),
                                                            counts, C.byref(written)))
         recs = [(f.kind, f.index, f.row, f.other_column, f.other_row) for f in out[: written.value]]
         return recs, (int(counts[0]), int(counts[1]), int(counts[2]))
+
+    def mock_prover_open(self, **desc) -> int:
+        """zk_mock_prover_open: the arguments of mock_prover_verify without advice / instances / cap / challenges -> handle.  Nothing passed here is referenced
+        afterwards, except device-resident fixed columns, which are borrowed until mock_prover_close"""
+        keep = []
+        d = self._mock_desc(keep, **desc)
+        mp = C.c_uint64()
+        self._ck(self.lib.zk_mock_prover_open(self.ctx, C.byref(d), C.byref(mp)))
+        return mp.value
+
+    def mock_prover_check(self, mp: int, advice, instances, *, cap: int = 0, challenges=None, struct_size: int | None = None, n_challenges: int | None = None):
+        """zk_mock_prover_check of one witness on an open handle: advice as (2^k, 4) uint64 Montgomery arrays or device buffers (all of one kind; None = a
+        NULL column), instances as canonical ints per column, challenges as canonical ints (None: none).  Returns what mock_prover_verify returns."""
+        keep = []
+        on_device = any(c is not None and not isinstance(c, np.ndarray) for c in advice)
+
+        def col_ptr(c):
+            if c is None:
+                return None
+            if on_device:
+                return _dptr(c)
+            a = np.ascontiguousarray(np.asarray(c).astype(np.uint64, copy=False))
+            keep.append(a)
+            return a.ctypes.data
+        adv = (C.c_void_p * max(1, len(advice)))(*[col_ptr(c) for c in advice])
+        inst = [np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in col) or bytes(32), dtype=np.uint8).copy() for col in instances]
+        iptr = (C.c_void_p * max(1, len(inst)))(*[a.ctypes.data for a in inst])
+        lens = np.ascontiguousarray(np.array([len(col) for col in instances] or [0], dtype=np.uint32))
+        w = MockWitness()
+        w.struct_size = C.sizeof(MockWitness) if struct_size is None else struct_size
+        w.advice_values = C.cast(adv, C.c_void_p).value
+        w.instances, w.instance_lens = C.cast(iptr, C.c_void_p).value, lens.ctypes.data
+        w.values_on_device = 1 if on_device else 0
+        ch = self._mock_challenges(challenges or [])
+        w.challenges = ch.ctypes.data if challenges else None
+        w.n_challenges = len(challenges or []) if n_challenges is None else n_challenges
+        out = (MockFailure * max(1, cap))()
+        counts = (C.c_uint64 * 3)()
+        written = C.c_size_t()
+        self._ck(self.lib.zk_mock_prover_check(self.ctx, C.c_uint64(mp), C.byref(w), out, C.c_size_t(cap), counts, C.byref(written)))
+        recs = [(f.kind, f.index, f.row, f.other_column, f.other_row) for f in out[: written.value]]
+        return recs, (int(counts[0]), int(counts[1]), int(counts[2]))
+
+    def mock_prover_info(self, mp: int, struct_size: int | None = None) -> dict:
+        """zk_mock_prover_info -> {n_tables, n_resident_tables, n_programs, n_edges, n_cells, device_bytes}"""
+        info = MockInfo()
+        info.struct_size = C.sizeof(MockInfo) if struct_size is None else struct_size
+        self._ck(self.lib.zk_mock_prover_info(self.ctx, C.c_uint64(mp), C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in MockInfo._fields_[1:]}
+
+    def mock_prover_close(self, mp: int):
+        self._ck(self.lib.zk_mock_prover_close(self.ctx, C.c_uint64(mp)))
 
     # -- keygen ----------------------------------------------------------------------------------
     def plonk_keygen_vk(self, k: int, fixed, perm_map_column, perm_map_row, srs_g_lagrange: int, struct_size: int | None = None, out=None):

@@ -49,6 +49,10 @@ int quotient_program_kernels(zk_ctx* ctx, uint64_t prog, uint32_t* n_kernels);
 int quotient_program_opmix(zk_ctx* ctx, uint64_t prog, uint32_t part, uint32_t counts[9]);
 int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written, const void* challenges = nullptr,
                        uint32_t n_challenges = 0, bool phased = false);
+int mock_prover_open(zk_ctx* ctx, const zk_mock_desc* d, uint64_t* mp);
+int mock_prover_check(zk_ctx* ctx, uint64_t mp, const zk_mock_witness* w, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written);
+int mock_prover_info(zk_ctx* ctx, uint64_t mp, zk_mock_info* info);
+int mock_prover_close(zk_ctx* ctx, uint64_t mp);
 int quotient_program_split(zk_ctx* ctx, uint64_t prog, uint32_t* low_cosets, uint32_t* n_instr_high, uint32_t* n_instr_low);
 int domain_coeff_to_coset_batch(zk_ctx* ctx, const void* const* coeffs, void* const* outs, size_t count, uint32_t k, uint32_t ek, uint32_t coset);
 int fr_interleave(zk_ctx* ctx, const void* const* h_cosets, size_t count, size_t n, void* d_out);
@@ -151,6 +155,8 @@ uint32_t zk_abi_struct_size(const char* name) ZK_ABI_TRY {
     if (!strcmp(name, "zk_mock_failure")) return (uint32_t)sizeof(zk_mock_failure);
     if (!strcmp(name, "zk_plonk_phases")) return (uint32_t)sizeof(zk_plonk_phases);
     if (!strcmp(name, "zk_plonk_keygen_desc")) return (uint32_t)sizeof(zk_plonk_keygen_desc);
+    if (!strcmp(name, "zk_mock_witness")) return (uint32_t)sizeof(zk_mock_witness);
+    if (!strcmp(name, "zk_mock_info")) return (uint32_t)sizeof(zk_mock_info);
     return 0;
 } ZK_ABI_CATCH_VALUE(nullptr, 0u)
 
@@ -249,6 +255,7 @@ void zk_ctx_destroy(zk_ctx* ctx) ZK_ABI_TRY {
         drop_pending_timers(ctx);
         release_twiddles(ctx);
         release_pks(ctx);
+        release_mock_sessions(ctx);             // (before the programs: a session releases the handles of the programs it compiled)
         release_programs(ctx);
         release_gtab(ctx);
         release_workspaces(ctx);
@@ -268,7 +275,7 @@ static int* tune_slot(zk_ctx* ctx, const char* key) {
         {"ntt_tile_log", &t.ntt_tile_log}, {"ntt_threads", &t.ntt_threads}, {"ntt_max_radix_log", &t.ntt_max_radix_log}, {"ntt_plan", &t.ntt_plan}, {"ntt_full_twiddle_max_log", &t.ntt_full_twiddle_max_log}, {"ntt_coset_table", &t.ntt_coset_table}, {"ntt_col_major", &t.ntt_col_major},
         {"vec_block", &t.vec_block}, {"quot_threads", &t.quot_threads},
         {"ntt_quarter_input", &t.ntt_quarter_input}, {"ntt_fuse_scale", &t.ntt_fuse_scale}, {"quot_piece_cosets", &t.quot_piece_cosets}, {"quot_factor_horner", &t.quot_factor_horner}, {"quot_degree_split", &t.quot_degree_split}, {"quot_group_factors", &t.quot_group_factors}, {"ntt_ws_limit_mb", &t.ntt_ws_limit_mb}, 
-        {"quot_jit", &t.quot_jit}, {"quot_jit_group", &t.quot_jit_group}, {"quot_jit_waves", &t.quot_jit_waves}, {"quot_remat_ops", &t.quot_remat_ops}, {"quot_remat_distance", &t.quot_remat_distance}, {"keygen_wgs", &t.keygen_wgs}};
+        {"quot_jit", &t.quot_jit}, {"quot_jit_group", &t.quot_jit_group}, {"quot_jit_waves", &t.quot_jit_waves}, {"quot_remat_ops", &t.quot_remat_ops}, {"quot_remat_distance", &t.quot_remat_distance}, {"keygen_wgs", &t.keygen_wgs}, {"mock_edge_wgs", &t.mock_edge_wgs}};
     for (auto& e : tab) if (!strcmp(e.k, key)) return e.v;
     return nullptr;
 }
@@ -542,6 +549,13 @@ int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const vo
     if (n_challenges > ZK_MAX_CHALLENGES) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_verify_phased: %u challenges, the quotient interpreter's constant bank is sized for %u", n_challenges, ZK_MAX_CHALLENGES);
     return mock_prover_verify(ctx, desc, out, cap, counts, n_written, challenges, n_challenges, true);
 } ZK_ABI_CATCH(ctx)
+// the session: one circuit resident, many witnesses (csrc/mockprover.hip)
+int zk_mock_prover_open(zk_ctx* ctx, const zk_mock_desc* desc, uint64_t* mp) ZK_ABI_TRY { ENTER; return mock_prover_open(ctx, desc, mp); } ZK_ABI_CATCH(ctx)
+int zk_mock_prover_check(zk_ctx* ctx, uint64_t mp, const zk_mock_witness* w, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written) ZK_ABI_TRY {
+    ENTER; return mock_prover_check(ctx, mp, w, out, cap, counts, n_written);
+} ZK_ABI_CATCH(ctx)
+int zk_mock_prover_info(zk_ctx* ctx, uint64_t mp, zk_mock_info* info) ZK_ABI_TRY { ENTER; return mock_prover_info(ctx, mp, info); } ZK_ABI_CATCH(ctx)
+int zk_mock_prover_close(zk_ctx* ctx, uint64_t mp) ZK_ABI_TRY { ENTER; return mock_prover_close(ctx, mp); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args) ZK_ABI_TRY { ENTER; ARGS_SIZE("zk_quotient_run_dev"); return quotient_run(ctx, prog, args, QuotRoute{}); } ZK_ABI_CATCH(ctx)
 int zk_quotient_run_coset_dev(zk_ctx* ctx, uint64_t prog, const zk_quotient_args* args, uint32_t coset) ZK_ABI_TRY {
     ENTER;

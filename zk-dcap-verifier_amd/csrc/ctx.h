@@ -60,6 +60,7 @@ struct Tune {
     int quot_jit = 0;            // zk_quotient_program_load: also generate straight-line kernels for the program with hiprtc (quotient_jit.hip) and run those instead of the interpreter; 0 = interpreter only; 1 = the kernels a single-GPU proof launches (the degree parts of a split program, else the whole program); 2 = whole program and parts
     int quot_jit_waves = 0;      // ... amdgpu_waves_per_eu of the generated kernels (0 = the compiler's choice; 4 = the interpreter's budget of 128 VGPRs, which costs some kernels a few spills)
     int keygen_wgs = 2048;       // zk_plonk_keygen_vk (pk.hip): the workgroups of 256 cells the mapping check and the sigma kernel launch at most; the cells beyond are a grid stride
+    int mock_edge_wgs = 2048;    // zk_mock_prover_open / _check (mockprover.hip): the workgroups of 256 edges the copy-edge kernels launch at most; the edges beyond are a grid stride
     int quot_jit_group = 200;    // ... products per generated kernel (swept 24 .. 400 on the sgx-shaped program, profiles/r05/run303: straight-line code streams well past the instruction cache; 200 = three to four kernels per program)
 };
 
@@ -125,6 +126,7 @@ struct TwiddleSet {           // per (omega, log_n)
 };
 
 struct QuotProgram;  // quotient.hip
+struct MockSession;  // mockprover.hip
 
 }  // namespace zk
 
@@ -140,6 +142,7 @@ struct zk_ctx {
     uint64_t twiddle_clock = 0;
     std::map<uint64_t, void*> coset_tables;                           // ntt.hip: (k, extended_k, coset) -> pre-scaling table of a coset transform
     std::map<uint64_t, std::shared_ptr<zk::QuotProgram>> programs;   // compiled micro-programs are immutable once loaded: contexts of one device may share them (zk_quotient_program_share)
+    std::map<uint64_t, std::shared_ptr<zk::MockSession>> mock_sessions;   // mockprover.hip: zk_mock_prover_open handles (ids are unique in the process, so another context's handle is unknown here)
     std::map<uint64_t, std::vector<uint32_t>> lookup_tie_hint;   // lookupperm.hip: columns whose rows tied on the sort window in the previous call of the same shape
     // workspaces (grow-only)
     zk::DevBuf ws_scalars, ws_sorted, ws_mid, ws_small, ws_sub0, ws_sub1, ws_cls0, ws_cls1, ws_tmp, ws_ntt, ws_ntt_in, ws_pts, ws_runs, ws_quot, ws_quot_state;
@@ -238,5 +241,6 @@ struct NttFuse {              // optional fused pre/post operations (EvaluationD
 int ntt_dev(zk_ctx* ctx, void* d_a, uint32_t log_n, const u256& omega, const NttFuse* fuse);
 void release_twiddles(zk_ctx* ctx);
 void release_programs(zk_ctx* ctx);
+void release_mock_sessions(zk_ctx* ctx);
 int quotient_program_share(zk_ctx* ctx, zk_ctx* owner, uint64_t owner_prog, uint64_t* prog);
 }  // namespace zk

@@ -18,6 +18,7 @@
 #include "ctx.h"
 #include "quotient.h"
 #include <algorithm>
+#include <atomic>
 #include <list>
 #include <random>
 #include <string>
@@ -174,6 +175,41 @@ ZK_KERNEL void mp_copy_kernel(const void* const* cols, const uint32_t* map_c, co
     if (cj >= n_cols || rj >= (1u << k)) atomicOr(bad, 1u);
     else if (cj != j || rj != row) f = Fr::eq(Fr::normalize(load_u256(cols[j], row)), Fr::normalize(load_u256(cols[cj], rj))) ? 0 : 1;
     flags[e] = f;
+}
+
+// ---- the session's copy pass (zk_mock_prover_open / zk_mock_prover_check): only the cells the mapping moves can fail, so they are listed once per circuit ----
+// 256 threads per workgroup, at most tune mock_edge_wgs workgroups, the rest a grid stride (as the keygen kernels of pk.hip).
+// flags[e] = the mapping sends cell e = j * 2^k + row to another cell; an entry outside the mapping's range sets *bad and is not flagged
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_edge_flag_kernel(const uint32_t* map_c, const uint32_t* map_r, uint32_t n_cols, uint32_t k, uint8_t* flags, uint32_t* bad) {
+    const uint64_t cells = (uint64_t)n_cols << k, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < cells; e += stride) {
+        const uint32_t cj = map_c[e], rj = map_r[e];
+        uint8_t f = 0;
+        if (cj >= n_cols || rj >= (1u << k)) atomicOr(bad, 1u);
+        else f = (((uint64_t)cj << k) | rj) != e ? 1 : 0;
+        flags[e] = f;
+    }
+}
+// edges[i] = (cell, image) of the i-th moved cell, both as column * 2^k + row (the mapping has fewer than 2^32 cells)
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_edge_gather_kernel(const uint32_t* moved, uint32_t n_edges, const uint32_t* map_c, const uint32_t* map_r, uint32_t k, uint2* edges) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_edges; i += stride) {
+        const uint32_t c = moved[i];
+        edges[i] = make_uint2(c, (map_c[c] << k) | map_r[c]);
+    }
+}
+// flags[i] = the two cells of edge i differ (values fully reduced, as mp_copy_kernel compares them)
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_copy_edges_kernel(const void* const* cols, const uint2* edges, uint32_t n_edges, uint32_t k, uint8_t* flags) {
+    const uint32_t stride = gridDim.x * blockDim.x, mask = (1u << k) - 1u;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_edges; i += stride) {
+        const uint2 e = edges[i];
+        flags[i] = Fr::eq(Fr::normalize(load_u256(cols[e.x >> k], e.x & mask)), Fr::normalize(load_u256(cols[e.y >> k], e.y & mask))) ? 0 : 1;
+    }
+}
+// out[i] = edges[picked[i]]: the (cell, image) pairs of the failing edges a caller takes records of
+ZK_KERNEL void ZK_LAUNCH_BOUNDS(256) mp_edge_pick_kernel(const uint32_t* picked, uint32_t count, const uint2* edges, uint2* out) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) out[i] = edges[picked[i]];
 }
 
 struct MpMem {                                   // every temporary of one call, returned to the device when the call ends (error returns included)
@@ -473,6 +509,448 @@ int mock_prover_verify(zk_ctx* ctx, const zk_mock_desc* d, zk_mock_failure* out,
         ZK_HIP(hipMemcpyAsync(idx.data(), copy_list, take_c * 4, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipStreamSynchronize(st));
         for (uint32_t e : idx) out[at++] = zk_mock_failure{2, e >> k, e & (n - 1), d->perm_map_column[e], d->perm_map_row[e]};
+    }
+    if (n_written) *n_written = at;
+    return ZK_OK;
+}
+
+// ---- the session: zk_mock_prover_open / _check / _info / _close (include/zkmi355.h) -----------------------------------------------------------------------------
+// Everything that depends on the circuit alone is done once and kept: the fixed columns, the copy edges, the compiled programs, the sorted resident tables and every
+// workspace of a check.  A check runs the witness-dependent kernels of mock_prover_verify on them and assembles the same records.
+struct MockSession {
+    zk_ctx* ctx = nullptr;
+    uint32_t k = 0, n = 0, u = 0, F = 0, A = 0, I = 0, L = 0, M = 0, n_challenges = 0, n_polys = 0, words = 0, n_edges = 0, n_programs = 0;
+    uint64_t cells = 0;
+    size_t bytes = 0;                                 // device memory owned
+    std::vector<void*> owned;
+    std::vector<uint64_t> progs;                      // program handles of ctx this session loaded
+    std::vector<uint32_t> perm_cols;
+    std::vector<const void*> fx;                      // fixed columns (owned, or borrowed with values_on_device)
+    std::vector<void*> inst, adv_stage;               // instance columns (refilled per check); staging for host advice (allocated by the first such check)
+    void *zero_col = nullptr, *work = nullptr, *d_cp = nullptr;
+    uint2* edges = nullptr;
+    uint8_t* flags = nullptr;                         // max(n_edges, u, L * u) flags: the passes of a check use it one after the other
+    uint32_t* tile_counts = nullptr;
+    DevBuf copy_list, gate_list, lookup_list, gate_bits, picked;   // sized by the number of failures: grow and are kept
+    uint64_t gate_prog = 0;
+    struct Table { uint64_t prog; bool resident; void* sorted; };
+    std::vector<Table> tables;                        // distinct table blobs
+    std::vector<uint64_t> input_prog;                 // per lookup
+    std::vector<uint32_t> table_of;                   // per lookup: index into tables
+    u256 theta;                                       // of the resident tables; never leaves the library
+    std::mt19937_64 rng;
+
+    void* get(size_t b) {
+        void* p = nullptr;
+        if (hipMalloc(&p, b ? b : 32) != hipSuccess) return nullptr;
+        owned.push_back(p);
+        bytes += b ? b : 32;
+        return p;
+    }
+    ~MockSession() {
+        (void)hipSetDevice(ctx->device);
+        for (void* p : owned) (void)hipFree(p);
+        for (DevBuf* b : {&copy_list, &gate_list, &lookup_list, &gate_bits, &picked}) b->release();
+        for (uint64_t h : progs) (void)quotient_program_release(ctx, h);
+    }
+};
+
+namespace {
+std::atomic<uint64_t> g_mock_session_id{1};
+
+uint32_t mp_edge_grid(zk_ctx* ctx, uint64_t count) {
+    const uint64_t want = (count + MP_T - 1) / MP_T, cap = ctx->tune.mock_edge_wgs > 0 ? (uint64_t)ctx->tune.mock_edge_wgs : 1;
+    return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+}
+// mp_compact on the session's buffers: `cnt` holds tiles + 1 counters, the list grows with the number of flagged indices and is kept
+int mp_compact_kept(zk_ctx* ctx, const uint8_t* d_flags, uint64_t count, uint32_t* cnt, DevBuf& list, uint32_t* total) {
+    const uint32_t tiles = (uint32_t)((count + MP_TILE - 1) / MP_TILE);
+    *total = 0;
+    if (!tiles) return ZK_OK;
+    ZK_LAUNCH(mp_count_kernel, tiles, MP_T, 0, ctx->stream, d_flags, count, cnt);
+    ZK_CHECK_LAUNCH();
+    ZK_LAUNCH(mp_scan_kernel, 1, MP_T, 0, ctx->stream, cnt, tiles);
+    ZK_CHECK_LAUNCH();
+    ZK_HIP(hipMemcpyAsync(total, cnt + tiles, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!*total) return ZK_OK;
+    if (list.ensure((size_t)*total * 4) != hipSuccess) return ctx->fail(ZK_ERR_HIP, "zk_mock_prover_check: device allocation failed");
+    ZK_LAUNCH(mp_scatter_kernel, tiles, MP_T, 0, ctx->stream, d_flags, count, (const uint32_t*)cnt, (uint32_t*)list.p);
+    ZK_CHECK_LAUNCH();
+    return ZK_OK;
+}
+// a compiled lookup program that reads fixed columns and constants only: no advice, no instance, no l_* column, no challenge, no power of X.  Read from the micro-ops
+// the executors run (quotient.h); whatever this reader does not recognise makes the table per-check, which is always correct.
+bool mp_reads_fixed_only(const QuotProgram& P) {
+    if (P.uses_xpow || P.part_hi || P.part_lo) return false;
+    for (const uint4& ins : P.code)
+        for (uint32_t src : {ins.y, ins.z, ins.w}) {
+            const uint32_t kind = src >> 28, pay = src & 0x0fffffffu;
+            if (kind == K_COL) { const uint32_t c = pay >> 8; if (c < P.col_fixed || c >= P.col_fixed + P.n_fixed) return false; }
+            else if (kind == K_CONST) { if (pay >= P.c_chal && pay < P.c_chal + P.n_challenges) return false; }
+            else if (kind != K_SLOT && kind != K_ACC && kind != K_NONE) return false;
+        }
+    return true;
+}
+MockSession* mp_session(zk_ctx* ctx, uint64_t mp, const char* fn) {
+    auto it = ctx->mock_sessions.find(mp);
+    if (it == ctx->mock_sessions.end()) { (void)ctx->fail(ZK_ERR_ARG, "%s: unknown handle %llu (closed, or opened on another context)", fn, (unsigned long long)mp); return nullptr; }
+    return it->second.get();
+}
+}  // namespace
+
+void release_mock_sessions(zk_ctx* ctx) { ctx->mock_sessions.clear(); }
+
+int mock_prover_open(zk_ctx* ctx, const zk_mock_desc* d, uint64_t* mp) {
+    if (!d || !mp) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: null descriptor / handle pointer");
+    if (d->struct_size != sizeof(zk_mock_desc))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: zk_mock_desc.struct_size %u, expected %zu (ABI version %u)", d->struct_size, sizeof(zk_mock_desc), ZK_ABI_VERSION);
+    const uint32_t k = d->k, F = d->n_fixed, A = d->n_advice, I = d->n_instance, L = d->n_lookups, M = d->n_perm_columns;
+    if (k < 2 || k > 26 || (uint64_t)d->blinding_factors + 1 >= (1ull << k))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: k = %u with %u blinding factors", k, d->blinding_factors);
+    const uint32_t n = 1u << k, u = n - d->blinding_factors - 1;
+    const size_t col_bytes = (size_t)32 << k;
+    if ((F && !d->fixed_values) || (L && (!d->lookup_input_zkq1 || !d->lookup_input_zkq1_len || !d->lookup_table_zkq1 || !d->lookup_table_zkq1_len)) ||
+        (M && (!d->perm_columns || !d->perm_map_column || !d->perm_map_row)) || !d->evaluator_zkq1)
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: missing column / program / mapping array");
+    for (uint32_t i = 0; i < F; i++) if (!d->fixed_values[i]) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: fixed column %u is NULL", i);
+    for (uint32_t j = 0; j < M; j++) {
+        const uint32_t ty = d->perm_columns[2 * j], ix = d->perm_columns[2 * j + 1];
+        if (ty > 2 || ix >= (ty == 0 ? A : ty == 1 ? F : I)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: permutation column %u = (%u, %u) out of range", j, ty, ix);
+    }
+    if (((uint64_t)M << k) >= (1ull << 32) || (uint64_t)L * u >= (1ull << 32)) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_open: more than 2^32 cells to check in one pass");
+    // every program's header before any work; the evaluator's challenge count is the circuit's, and every blob must declare the same
+    uint32_t n_challenges = 0;
+    auto header = [&](const void* blob, size_t len, bool evaluator, const char* what, uint32_t i) -> int {
+        if (!blob || len < 48 || (len & 3)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: bad %s blob %u", what, i);
+        uint32_t w[7];
+        memcpy(w, blob, sizeof w);
+        if (w[0] != 0x31514B5Au) return ctx->fail(ZK_ERR_PROGRAM, "zk_mock_prover_open: %s blob %u: bad magic", what, i);
+        if (evaluator) n_challenges = w[6];
+        if (w[6] != n_challenges) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: %s blob %u declares %u challenges, the evaluator %u", what, i, w[6], n_challenges);
+        if (w[6] > ZK_MAX_CHALLENGES) return ctx->fail(ZK_ERR_LIMIT, "zk_mock_prover_open: %u challenges, the quotient interpreter's constant bank is sized for %u", w[6], ZK_MAX_CHALLENGES);
+        if (w[1] != k || (!evaluator && w[2] != k)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: %s blob %u is for k = %u / extended_k = %u, not k = %u", what, i, w[1], w[2], k);
+        if (w[3] != F || w[4] != A || w[5] != I) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: %s blob %u has %u / %u / %u fixed / advice / instance columns, the descriptor %u / %u / %u",
+                                                                   what, i, w[3], w[4], w[5], F, A, I);
+        return ZK_OK;
+    };
+    int rc = header(d->evaluator_zkq1, d->evaluator_zkq1_len, true, "evaluator", 0);
+    for (uint32_t l = 0; l < L && !rc; l++) {
+        rc = header(d->lookup_input_zkq1[l], d->lookup_input_zkq1_len[l], false, "lookup input", l);
+        if (!rc) rc = header(d->lookup_table_zkq1[l], d->lookup_table_zkq1_len[l], false, "lookup table", l);
+    }
+    if (rc) return rc;
+
+    MpTimer timer(ctx, "mock_open");
+    std::shared_ptr<MockSession> S(new MockSession());               // an error return frees what the session holds so far
+    S->ctx = ctx; S->k = k; S->n = n; S->u = u; S->F = F; S->A = A; S->I = I; S->L = L; S->M = M; S->n_challenges = n_challenges;
+    S->cells = (uint64_t)M << k;
+    if (M) S->perm_cols.assign(d->perm_columns, d->perm_columns + 2 * (size_t)M);
+    std::random_device rd;
+    S->rng.seed(((uint64_t)rd() << 32) ^ rd());
+    S->theta = mp_random_nonzero(S->rng);
+    hipStream_t st = ctx->stream;
+    const char* oom = "zk_mock_prover_open: device allocation failed";
+    // ---- fixed columns, the instance columns a check refills, the zero column, the work column ------------------------------------------------------------------
+    S->fx.resize(F);
+    for (uint32_t i = 0; i < F; i++) {
+        if (d->values_on_device) { S->fx[i] = d->fixed_values[i]; continue; }
+        void* p = S->get(col_bytes);
+        if (!p) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+        ZK_HIP(hipMemcpyAsync(p, d->fixed_values[i], col_bytes, hipMemcpyHostToDevice, st));
+        S->fx[i] = p;
+    }
+    S->inst.resize(I);
+    for (uint32_t c = 0; c < I; c++) if (!(S->inst[c] = S->get(col_bytes))) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+    S->zero_col = S->get(col_bytes);
+    S->work = S->get(col_bytes);
+    if (!S->zero_col || !S->work) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+    ZK_HIP(hipMemsetAsync(S->zero_col, 0, col_bytes, st));
+    ZK_HIP(hipStreamSynchronize(st));                                 // (the caller's fixed columns are on the device)
+
+    // ---- copy edges: planes up, range check + flag, compact (cell order), gather the pairs; the planes go when `mem` does -------------------------------------------
+    if (M) {
+        MpMem mem;
+        const size_t cells = (size_t)S->cells;
+        uint32_t* d_mc = (uint32_t*)mem.get(cells * 4);
+        uint32_t* d_mr = (uint32_t*)mem.get(cells * 4);
+        uint8_t* flags = (uint8_t*)mem.get(cells);
+        uint32_t* d_bad = (uint32_t*)mem.get(4);
+        if (!d_mc || !d_mr || !flags || !d_bad) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+        ZK_HIP(hipMemcpyAsync(d_mc, d->perm_map_column, cells * 4, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_mr, d->perm_map_row, cells * 4, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemsetAsync(d_bad, 0, 4, st));
+        ZK_LAUNCH(mp_edge_flag_kernel, mp_edge_grid(ctx, cells), MP_T, 0, st, (const uint32_t*)d_mc, (const uint32_t*)d_mr, M, k, flags, d_bad);
+        ZK_CHECK_LAUNCH();
+        uint32_t bad = 0;
+        ZK_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        if (bad) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_open: a copy-mapping entry is out of range (column >= %u or row >= 2^%u)", M, k);
+        uint32_t* moved = nullptr;
+        rc = mp_compact(ctx, mem, flags, cells, &moved, &S->n_edges);
+        if (rc) return rc;
+        if (S->n_edges) {
+            S->edges = (uint2*)S->get((size_t)S->n_edges * sizeof(uint2));
+            if (!S->edges) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+            ZK_LAUNCH(mp_edge_gather_kernel, mp_edge_grid(ctx, S->n_edges), MP_T, 0, st, (const uint32_t*)moved, S->n_edges, (const uint32_t*)d_mc, (const uint32_t*)d_mr, k, S->edges);
+            ZK_CHECK_LAUNCH();
+            ZK_HIP(hipStreamSynchronize(st));
+        }
+        S->d_cp = S->get((size_t)M * sizeof(void*));
+        if (!S->d_cp) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+    }
+
+    // ---- programs: the gates, and one per distinct lookup blob -----------------------------------------------------------------------------------------------
+    rc = quotient_program_load_gates(ctx, d->evaluator_zkq1, d->evaluator_zkq1_len, &S->gate_prog, &S->n_polys);
+    if (rc) return rc;
+    if (S->gate_prog) { S->progs.push_back(S->gate_prog); S->n_programs++; }
+    S->words = (S->n_polys + 31) / 32;
+    std::map<std::string, uint64_t> loaded;                           // blob -> program
+    auto load = [&](const void* blob, size_t len, uint64_t* h) -> int {
+        const std::string key((const char*)blob, len);
+        auto it = loaded.find(key);
+        if (it != loaded.end()) { *h = it->second; return ZK_OK; }
+        int rc_ = quotient_program_load(ctx, blob, len, h);
+        if (rc_) return rc_;
+        S->progs.push_back(*h);
+        S->n_programs++;
+        loaded.emplace(key, *h);
+        return ZK_OK;
+    };
+    std::map<uint64_t, uint32_t> table_index;                         // table program -> index into S->tables
+    S->input_prog.resize(L);
+    S->table_of.resize(L);
+    for (uint32_t l = 0; l < L; l++) {
+        uint64_t tp = 0;
+        rc = load(d->lookup_input_zkq1[l], d->lookup_input_zkq1_len[l], &S->input_prog[l]);
+        if (!rc) rc = load(d->lookup_table_zkq1[l], d->lookup_table_zkq1_len[l], &tp);
+        if (rc) return rc;
+        auto it = table_index.find(tp);
+        if (it == table_index.end()) {
+            void* sorted = S->get(col_bytes);
+            if (!sorted) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+            it = table_index.emplace(tp, (uint32_t)S->tables.size()).first;
+            S->tables.push_back(MockSession::Table{tp, mp_reads_fixed_only(*ctx->programs.at(tp)), sorted});
+        }
+        S->table_of[l] = it->second;
+    }
+    // ---- resident tables: compressed with the handle's theta and sorted once ---------------------------------------------------------------------------------
+    {
+        const u256 one = Fr::one();
+        std::vector<const void*> ad(A, S->zero_col), in(I, S->zero_col);     // (a resident program reads neither)
+        std::vector<u256> no_challenges(std::max<uint32_t>(n_challenges, 1), Fr::zero());
+        zk_quotient_args qa;
+        ZK_STRUCT_INIT(qa);
+        qa.fixed = S->fx.data(); qa.advice = ad.data(); qa.instance = in.data();
+        qa.l0 = qa.l_last = qa.l_active_row = S->zero_col;
+        qa.challenges = no_challenges.data(); qa.beta = &one; qa.gamma = &one; qa.theta = &S->theta; qa.y = &one;
+        qa.out = S->work;
+        for (auto& t : S->tables) {
+            if (!t.resident) continue;
+            rc = quotient_run(ctx, t.prog, &qa, QuotRoute{});
+            if (rc) return rc;
+            ZK_LAUNCH(mp_table_init_kernel, (n + 255) / 256, 256, 0, st, (const void*)S->work, u, n, t.sorted);
+            ZK_CHECK_LAUNCH();
+            rc = mp_sort(ctx, t.sorted, k);
+            if (rc) return rc;
+        }
+    }
+    // ---- the workspaces of a check ----------------------------------------------------------------------------------------------------------------------------
+    const uint64_t max_flags = std::max<uint64_t>(std::max<uint64_t>(S->n_edges, u), (uint64_t)L * u);
+    S->flags = (uint8_t*)S->get(max_flags);
+    S->tile_counts = (uint32_t*)S->get(((max_flags + MP_TILE - 1) / MP_TILE + 1) * 4);
+    if (!S->flags || !S->tile_counts) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+    ZK_HIP(hipStreamSynchronize(st));
+    timer.done();
+    const uint64_t id = (0x4d50ull << 48) | g_mock_session_id.fetch_add(1);
+    ctx->mock_sessions[id] = S;
+    *mp = id;
+    return ZK_OK;
+}
+
+int mock_prover_info(zk_ctx* ctx, uint64_t mp, zk_mock_info* info) {
+    if (!info) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_info: null output");
+    if (info->struct_size != sizeof(zk_mock_info))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_info: zk_mock_info.struct_size %u, expected %zu (ABI version %u)", info->struct_size, sizeof(zk_mock_info), ZK_ABI_VERSION);
+    const MockSession* S = mp_session(ctx, mp, "zk_mock_prover_info");
+    if (!S) return ZK_ERR_ARG;
+    info->n_tables = (uint32_t)S->tables.size();
+    info->n_resident_tables = 0;
+    for (auto& t : S->tables) info->n_resident_tables += t.resident ? 1 : 0;
+    info->n_programs = S->n_programs;
+    info->n_edges = S->n_edges;
+    info->n_cells = S->cells;
+    info->device_bytes = S->bytes + S->copy_list.cap + S->gate_list.cap + S->lookup_list.cap + S->gate_bits.cap + S->picked.cap;
+    return ZK_OK;
+}
+
+int mock_prover_close(zk_ctx* ctx, uint64_t mp) {
+    if (!mp_session(ctx, mp, "zk_mock_prover_close")) return ZK_ERR_ARG;
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->mock_sessions.erase(mp);
+    return ZK_OK;
+}
+
+int mock_prover_check(zk_ctx* ctx, uint64_t mp, const zk_mock_witness* w, zk_mock_failure* out, size_t cap, uint64_t counts[3], size_t* n_written) {
+    if (!w) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: null witness");
+    if (w->struct_size != sizeof(zk_mock_witness))
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: zk_mock_witness.struct_size %u, expected %zu (ABI version %u)", w->struct_size, sizeof(zk_mock_witness), ZK_ABI_VERSION);
+    if (!counts || (cap && !out)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: null counts / output");
+    MockSession* S = mp_session(ctx, mp, "zk_mock_prover_check");
+    if (!S) return ZK_ERR_ARG;
+    const uint32_t k = S->k, n = S->n, u = S->u, A = S->A, I = S->I, L = S->L, M = S->M;
+    const size_t col_bytes = (size_t)32 << k;
+    if (A && !w->advice_values) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: missing advice column array");
+    for (uint32_t i = 0; i < A; i++) if (!w->advice_values[i]) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: advice column %u is NULL", i);
+    if (w->n_challenges != S->n_challenges)
+        return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: the circuit's blobs declare %u challenges, the caller passed %u", S->n_challenges, w->n_challenges);
+    if (w->n_challenges && !w->challenges) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: %u challenges and a null array", w->n_challenges);
+    for (uint32_t c = 0; c < I; c++) {
+        const uint32_t len = w->instance_lens ? w->instance_lens[c] : 0;
+        if (len > n || (len && (!w->instances || !w->instances[c]))) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: instance column %u: %u values", c, len);
+    }
+    hipStream_t st = ctx->stream;
+    const char* oom = "zk_mock_prover_check: device allocation failed";
+    // ---- the witness on the device: instances to Montgomery form into the handle's columns, advice as given or staged ---------------------------------------------
+    std::vector<u256> host_col;
+    for (uint32_t c = 0; c < I; c++) {
+        const uint32_t len = w->instance_lens ? w->instance_lens[c] : 0;
+        host_col.assign(n, Fr::zero());
+        for (uint32_t i = 0; i < len; i++) {
+            u256 v;
+            memcpy(&v, (const char*)w->instances[c] + 32 * (size_t)i, 32);
+            if (!Fr::eq(Fr::reduce_once(v), v)) return ctx->fail(ZK_ERR_ARG, "zk_mock_prover_check: instance %u of column %u is not canonical", i, c);
+            host_col[i] = Fr::to_mont(v);
+        }
+        ZK_HIP(hipMemcpyAsync(S->inst[c], host_col.data(), col_bytes, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipStreamSynchronize(st));                             // (host_col is refilled for the next column)
+    }
+    std::vector<const void*> ad(A), in(S->inst.begin(), S->inst.end());
+    if (w->values_on_device) for (uint32_t i = 0; i < A; i++) ad[i] = w->advice_values[i];
+    else {
+        while (S->adv_stage.size() < A) {
+            void* p = S->get(col_bytes);
+            if (!p) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+            S->adv_stage.push_back(p);
+        }
+        for (uint32_t i = 0; i < A; i++) {
+            ZK_HIP(hipMemcpyAsync(S->adv_stage[i], w->advice_values[i], col_bytes, hipMemcpyHostToDevice, st));
+            ad[i] = S->adv_stage[i];
+        }
+        ZK_HIP(hipStreamSynchronize(st));                             // (the caller's columns are not read after the call, whatever passes the circuit has)
+    }
+    const u256 one = Fr::one(), r = mp_random_nonzero(S->rng), theta = mp_random_nonzero(S->rng);
+    zk_quotient_args qa;
+    ZK_STRUCT_INIT(qa);
+    qa.fixed = S->fx.data(); qa.advice = ad.data(); qa.instance = in.data();
+    qa.l0 = qa.l_last = qa.l_active_row = S->zero_col;
+    qa.challenges = w->n_challenges ? w->challenges : (const void*)&one; qa.beta = &one; qa.gamma = &one; qa.theta = &theta; qa.y = &r;
+    const uint32_t blk = 256;
+    int rc;
+
+    // ---- copies: one thread per edge ------------------------------------------------------------------------------------------------------------------------------
+    uint32_t n_copy = 0;
+    if (S->n_edges) {
+        MpTimer t(ctx, "mock_copy_edges");
+        std::vector<const void*> cp(M);
+        for (uint32_t j = 0; j < M; j++) {
+            const uint32_t ty = S->perm_cols[2 * j], ix = S->perm_cols[2 * j + 1];
+            cp[j] = ty == 0 ? ad[ix] : ty == 1 ? S->fx[ix] : in[ix];
+        }
+        ZK_HIP(hipMemcpyAsync(S->d_cp, cp.data(), (size_t)M * sizeof(void*), hipMemcpyHostToDevice, st));
+        ZK_LAUNCH(mp_copy_edges_kernel, mp_edge_grid(ctx, S->n_edges), MP_T, 0, st, (const void* const*)S->d_cp, (const uint2*)S->edges, S->n_edges, k, S->flags);
+        ZK_CHECK_LAUNCH();
+        rc = mp_compact_kept(ctx, S->flags, S->n_edges, S->tile_counts, S->copy_list, &n_copy);
+        if (rc) return rc;
+        t.done();
+    }
+
+    // ---- gates: detection over every row, attribution on the failing rows (as mock_prover_verify) -------------------------------------------------------------------
+    const uint32_t n_polys = S->n_polys, words = S->words;
+    uint32_t n_rows = 0;
+    std::vector<uint32_t> rows, bits;
+    if (n_polys) {
+        {
+            MpTimer t(ctx, "mock_gates");
+            qa.out = S->work;
+            rc = quotient_run(ctx, S->gate_prog, &qa, QuotRoute{});
+            if (rc) return rc;
+            ZK_LAUNCH(mp_nonzero_kernel, (u + blk - 1) / blk, blk, 0, st, (const void*)S->work, u, S->flags);
+            ZK_CHECK_LAUNCH();
+            rc = mp_compact_kept(ctx, S->flags, u, S->tile_counts, S->gate_list, &n_rows);
+            if (rc) return rc;
+            t.done();
+        }
+        if (n_rows) {
+            MpTimer t(ctx, "mock_gate_rows");
+            if (S->gate_bits.ensure((size_t)n_rows * words * 4) != hipSuccess) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+            const QuotRowList rl{(const uint32_t*)S->gate_list.p, n_rows, (uint32_t*)S->gate_bits.p, words};
+            QuotRoute route;
+            route.rows = &rl;
+            rc = quotient_run(ctx, S->gate_prog, &qa, route);
+            if (rc) return rc;
+            rows.resize(n_rows);
+            bits.resize((size_t)n_rows * words);
+            ZK_HIP(hipMemcpyAsync(rows.data(), S->gate_list.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+            ZK_HIP(hipMemcpyAsync(bits.data(), S->gate_bits.p, bits.size() * 4, hipMemcpyDeviceToHost, st));
+            ZK_HIP(hipStreamSynchronize(st));
+            t.done();
+        }
+    }
+
+    // ---- lookups: per-check tables compressed with this call's theta and sorted once; every input with its table's theta ---------------------------------------------
+    uint32_t n_lookup = 0;
+    if (L) {
+        MpTimer t(ctx, "mock_lookups");
+        for (auto& tb : S->tables) {
+            if (tb.resident) continue;
+            qa.theta = &theta;
+            qa.out = S->work;
+            rc = quotient_run(ctx, tb.prog, &qa, QuotRoute{});
+            if (rc) return rc;
+            ZK_LAUNCH(mp_table_init_kernel, (n + blk - 1) / blk, blk, 0, st, (const void*)S->work, u, n, tb.sorted);
+            ZK_CHECK_LAUNCH();
+            rc = mp_sort(ctx, tb.sorted, k);
+            if (rc) return rc;
+        }
+        for (uint32_t l = 0; l < L; l++) {
+            const MockSession::Table& tb = S->tables[S->table_of[l]];
+            qa.theta = tb.resident ? &S->theta : &theta;
+            qa.out = S->work;
+            rc = quotient_run(ctx, S->input_prog[l], &qa, QuotRoute{});
+            if (rc) return rc;
+            ZK_LAUNCH(mp_search_kernel, (u + blk - 1) / blk, blk, 0, st, (const void*)S->work, (const void*)tb.sorted, k, u, S->flags + (size_t)l * u);
+            ZK_CHECK_LAUNCH();
+        }
+        rc = mp_compact_kept(ctx, S->flags, (uint64_t)L * u, S->tile_counts, S->lookup_list, &n_lookup);
+        if (rc) return rc;
+        t.done();
+    }
+
+    // ---- records, in mock_prover_verify's order; a copy's other cell comes from the packed edge ---------------------------------------------------------------------
+    uint64_t n_gate = 0;
+    for (uint32_t wd : bits) n_gate += (uint64_t)__builtin_popcount(wd);
+    counts[0] = n_gate; counts[1] = n_lookup; counts[2] = n_copy;
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_rows && at < cap; i++)
+        for (uint32_t p = 0; p < n_polys && at < cap; p++)
+            if ((bits[(size_t)i * words + p / 32] >> (p & 31)) & 1u) out[at++] = zk_mock_failure{0, p, rows[i], 0, 0};
+    const size_t take_l = std::min<size_t>(cap - at, n_lookup);
+    if (take_l) {
+        std::vector<uint32_t> idx(take_l);
+        ZK_HIP(hipMemcpyAsync(idx.data(), S->lookup_list.p, take_l * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        for (uint32_t e : idx) out[at++] = zk_mock_failure{1, e / u, e % u, 0, 0};
+    }
+    const size_t take_c = std::min<size_t>(cap - at, n_copy);
+    if (take_c) {
+        if (S->picked.ensure(take_c * sizeof(uint2)) != hipSuccess) return ctx->fail(ZK_ERR_HIP, "%s", oom);
+        ZK_LAUNCH(mp_edge_pick_kernel, mp_edge_grid(ctx, take_c), MP_T, 0, st, (const uint32_t*)S->copy_list.p, (uint32_t)take_c, (const uint2*)S->edges, (uint2*)S->picked.p);
+        ZK_CHECK_LAUNCH();
+        std::vector<uint2> pairs(take_c);
+        ZK_HIP(hipMemcpyAsync(pairs.data(), S->picked.p, take_c * sizeof(uint2), hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        for (const uint2& e : pairs) out[at++] = zk_mock_failure{2, e.x >> k, e.x & (n - 1), e.y >> k, e.y & (n - 1)};
     }
     if (n_written) *n_written = at;
     return ZK_OK;

@@ -153,3 +153,100 @@ class NativeMockProver:
         f = self.verify()
         if f:
             raise VerifyFailure("; ".join(f[:5]) + (f" (+{len(f) - 5} more)" if len(f) > 5 else ""))
+
+
+class NativeMockSession:
+    """One circuit resident on the GPU, any number of witnesses checked against it: zk_mock_prover_open once, zk_mock_prover_check per witness (csrc/mockprover.hip,
+    DESIGN.md 3.6).  open uploads the fixed columns, reduces Assembly.map_c / map_r to the copy edges, compiles the gate and lookup programs and sorts the lookup
+    tables that read fixed columns only; a check then costs its kernels.  The records are NativeMockProver's, record for record.  Advice may be host arrays, integer
+    lists or device buffers - the buffers a following prove adopts are read, never written.  Use as a context manager, or close() it."""
+
+    KINDS = NativeMockProver.KINDS
+
+    def __init__(self, k: int, cs: ConstraintSystem, fixed: Sequence, assembly: Assembly | None = None, backend=None):
+        from .._lib import default_backend
+        from .keygen import compile_program, compressor_program
+        self.k, self.n, self.cs, self.assembly = k, 1 << k, cs, assembly
+        self.backend = backend or default_backend()
+        self.fixed = [self._conv(c) for c in fixed]                          # (device-resident fixed columns are borrowed by the handle: kept alive here)
+        ek = k
+        while (1 << ek) < self.n * (cs.degree() - 1):
+            ek += 1
+        perm = list(assembly.columns) if assembly is not None else []
+        self._counts = None
+        self.handle = 0
+        self.handle = self.backend.mock_prover_open(
+            k=k, blinding_factors=cs.blinding_factors(), n_fixed=cs.num_fixed_columns, n_advice=cs.num_advice_columns, n_instance=cs.num_instance_columns,
+            perm_columns=perm, evaluator_blob=compile_program(cs, k, ek).to_blob(),
+            lookup_input_blobs=[compressor_program(cs, k, lk.input_expressions).to_blob() for lk in cs.lookups],
+            lookup_table_blobs=[compressor_program(cs, k, lk.table_expressions).to_blob() for lk in cs.lookups],
+            fixed=self.fixed, perm_map_column=assembly.map_c if perm else None, perm_map_row=assembly.map_r if perm else None)
+
+    @staticmethod
+    def _conv(c):
+        if not isinstance(c, (np.ndarray, list, tuple)):
+            return c                                                         # a device buffer
+        if isinstance(c, np.ndarray) and c.dtype == np.uint64:
+            return np.ascontiguousarray(c).reshape(-1, 4)
+        return fr_mont_array([int(v) % R_MOD for v in c])
+
+    def _run(self, advice, instances, challenges, cap):
+        recs, counts = self.backend.mock_prover_check(self.handle, [self._conv(c) for c in advice], [[int(v) for v in c] for c in instances], cap=cap,
+                                                      challenges=None if challenges is None else [int(c) % R_MOD for c in challenges])
+        return [MockFailure(self.KINDS[r[0]], *r[1:]) for r in recs], counts
+
+    def check(self, advice: Sequence, instances: Sequence[Sequence[int]], challenges: Sequence[int] | None = None, cap: int | None = None) -> List[MockFailure]:
+        """the structured records of one witness: all of them (a second device check when there are more than 4096), or the first `cap`"""
+        if cap is not None:
+            recs, self._counts = self._run(advice, instances, challenges, cap)
+            return recs
+        recs, counts = self._run(advice, instances, challenges, 4096)
+        if sum(counts) > len(recs):
+            recs, counts = self._run(advice, instances, challenges, sum(counts))
+        self._counts = counts
+        return recs
+
+    @property
+    def counts(self):
+        """(gate, lookup, copy) failures of the last check, exact"""
+        return self._counts
+
+    def verify(self, advice, instances, challenges=None) -> List[str]:
+        """MockProver.verify()'s strings for this witness, one per record, in its order"""
+        out = []
+        for f in self.check(advice, instances, challenges):
+            if f.kind == "gate":
+                out.append(f"gate {f.index} not satisfied on row {f.row}")
+            elif f.kind == "lookup":
+                out.append(f"lookup {f.index}: input of row {f.row} is not in the table")
+            else:
+                out.append(f"copy constraint violated: column {f.index} row {f.row} != column {f.other_column} row {f.other_row}")
+        return out
+
+    def assert_satisfied(self, advice, instances, challenges=None) -> None:
+        f = self.verify(advice, instances, challenges)
+        if f:
+            raise VerifyFailure("; ".join(f[:5]) + (f" (+{len(f) - 5} more)" if len(f) > 5 else ""))
+
+    @property
+    def info(self) -> dict:
+        """zk_mock_prover_info: copy edges kept against mapping cells, distinct / resident tables, compiled programs, device bytes"""
+        return self.backend.mock_prover_info(self.handle)
+
+    def close(self):
+        if self.handle and self.backend.ctx:
+            h, self.handle = self.handle, 0
+            self.backend.mock_prover_close(h)
+        self.handle = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
