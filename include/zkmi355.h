@@ -577,8 +577,9 @@ int zk_mock_prover_verify_phased(zk_ctx* ctx, const zk_mock_desc* desc, const vo
  * n_challenges must equal what every blob declares (0: the single-phase case; then challenges may be NULL).
  * ZK_ERR_ARG from zk_mock_prover_check: a wrong struct_size, a NULL advice column, a non-canonical instance, a wrong challenge count, a handle that is closed or
  * belongs to another context.  After any error the handle stays usable.
- * Handles are per context: zk_ctx_destroy releases those still open; zk_plonk_trim does not touch them.  Timing labels (zk_timing_get): "mock_open",
- * "mock_copy_edges", and zk_mock_prover_verify's "mock_gates", "mock_gate_rows", "mock_lookups".  Tunable "mock_edge_wgs": the workgroups (of 256 edges per step) the
+ * Handles are per context: zk_ctx_destroy releases those still open; zk_plonk_trim does not touch them.  Timing labels (zk_timing_get): "mock_open" (recorded by
+ * zk_mock_prover_open alone); per check "mock_copy_edges", "mock_gates", "mock_gate_rows", "mock_lookups" - zk_mock_prover_verify(_phased) records the last three for
+ * the same passes, and "mock_copies" for its dense copy pass.  Tunable "mock_edge_wgs": the workgroups (of 256 edges per step) the
  * edge kernels launch at most, 2048 by default; the edges beyond are a grid stride. */
 typedef struct zk_mock_witness zk_mock_witness;
 typedef struct zk_mock_info zk_mock_info;

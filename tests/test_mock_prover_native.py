@@ -12,7 +12,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import EMU_SO, ROOT
 from zk_dcap_verifier_amd import plonk
 from zk_dcap_verifier_amd._lib import MockDesc, MockFailure, ZkError
 from zk_dcap_verifier_amd.fields import R_MOD, fr_int_array, fr_mont, fr_mont_array
@@ -139,6 +139,43 @@ def test_argument_errors_leave_the_context_usable_emulated(emu):
     assert nm.verify() == want
     cs, fixed, asm, advice, instances = toy_circuit(6)
     assert NativeMockProver.run(6, cs, fixed, advice, instances, asm, backend=emu).counts == (0, 0, 0)
+
+
+def test_one_shot_call_returns_what_it_took_emulated(emu):
+    """zk_mock_prover_verify checks its witness on a session of its own that ends with the call: whichever way the call returns, no device block stays behind, and
+    no handle either"""
+    import test_mock_session as tms
+    live = C.CDLL(EMU_SO).zk_test_live_device_allocs
+    live.restype = C.c_long
+    k = 5
+    clean, _ = tms.rich(k)
+    case, want = tms.rich(k, tms.PLANTS["all"])
+    g, l, c = tms.KINDS["all"]
+    with tms.open_session(emu, clean) as s:          # the ids a one-shot call that filed its session would draw come after this one
+        h0 = s.handle
+    nm = NativeMockProver.run(k, case.cs, case.fixed, case.advice, case.instances, case.asm, backend=emu)
+    assert nm._check(g + l + c) == (want, (g, l, c))                 # warm-up: the context's own workspaces reach their sizes
+    before = live()
+    assert NativeMockProver.run(k, clean.cs, clean.fixed, clean.advice, clean.instances, clean.asm, backend=emu)._check(8) == ([], (0, 0, 0))
+    assert live() == before
+    assert nm._check(g + l + 2) == (want[: g + l + 2], (g, l, c))    # `cap` inside the copy records
+    assert live() == before
+
+    def refused(**over):
+        with pytest.raises(ZkError) as e:
+            emu.mock_prover_verify(cap=4, **dict(nm.args, **over))
+        assert e.value.code == ERR_ARG and live() == before
+        return str(e.value)
+    bad_map = np.array(case.asm.map_c, dtype=np.int64)
+    bad_map[1, 3] = len(case.asm.columns)
+    assert "copy-mapping entry is out of range" in refused(perm_map_column=bad_map)
+    assert "not canonical" in refused(instances=[[R_MOD] + list(nm.instances[0][1:])])
+    assert "advice column 1 is NULL" in refused(advice=[nm.advice[0], None] + nm.advice[2:])
+    assert nm._check(g + l + c) == (want, (g, l, c)) and live() == before
+    for h in range(h0, h0 + 16):
+        with pytest.raises(ZkError) as e:
+            emu.mock_prover_info(h)
+        assert e.value.code == ERR_ARG
 
 
 def test_rust_mock_structs_match_the_header():
