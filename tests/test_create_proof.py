@@ -29,9 +29,11 @@ def _golden(name=GOLDEN_PROOF):
 
 
 
-def toy_circuit(k, with_lookup=True, tamper=None):
+def toy_circuit(k, with_lookup=True, tamper=None, extreme=None):
     """3 gates (one with a rotation, one querying the instance column), copy constraints over 3 advice + 1 instance column (2 permutation sets at degree 5),
-    one lookup whose input is a product expression.  Returns (cs, fixed columns, assembly, advice columns, instances)."""
+    one lookup whose input is a product expression.  Returns (cs, fixed columns, assembly, advice columns, instances).
+    extreme: a witness at the edge of what the gates allow, still satisfied — "zero_b": b = 0 on every row, so c = a * b is a second all-zero column and both instances
+    are 0; "max": a runs through 8 .. 15 (the top of the lookup table) and b = r - 1 on every row, so c = -a."""
     n = 1 << k
     cs = plonk.ConstraintSystem(num_fixed_columns=4, num_advice_columns=3, num_instance_columns=1)
     a, b, c = Advice(0), Advice(1), Advice(2)
@@ -46,6 +48,11 @@ def toy_circuit(k, with_lookup=True, tamper=None):
     u = cs.usable_rows(k)
     A = [(i % 8) + 1 for i in range(n)]
     B = [((i // 2) % 5) + 2 for i in range(n)]                       # b[2i+1] == b[2i]
+    assert extreme in (None, "zero_b", "max"), extreme
+    if extreme == "zero_b":
+        B = [0] * n
+    elif extreme == "max":
+        A, B = [(i % 8) + 8 for i in range(n)], [R_MOD - 1] * n
     C = [x * y % R_MOD for x, y in zip(A, B)]
     Q = [1 if i < u else 0 for i in range(n)]
     Q2 = [1 if (i % 8 != 7 and i + 1 < u) else 0 for i in range(n)]

@@ -18,8 +18,9 @@ import random_circuits as rc
 import test_create_proof as tcp
 
 
-def graded_circuit(k, t):
-    """a SATISFIED circuit of degree 3 + t: the product gate q * (a * b - c) times a^t, a running-sum gate with a rotation, copy constraints over all three advice columns"""
+def graded_circuit(k, t, extreme=None):
+    """a SATISFIED circuit of degree 3 + t: the product gate q * (a * b - c) times a^t, a running-sum gate with a rotation, copy constraints over all three advice columns.
+    extreme (still satisfied): "zero_b": b = 0 and hence c = 0 on every row; "max": b = r - 1 on every row, c = -a"""
     n = 1 << k
     cs = plonk.ConstraintSystem(num_fixed_columns=2, num_advice_columns=3, num_instance_columns=1)
     a, b, c = Advice(0), Advice(1), Advice(2)
@@ -34,6 +35,9 @@ def graded_circuit(k, t):
     u = cs.usable_rows(k)
     A = [(i % 8) + 1 for i in range(n)]
     B = [((i // 2) % 5) + 2 for i in range(n)]
+    assert extreme in (None, "zero_b", "max"), extreme
+    if extreme:
+        B = [0 if extreme == "zero_b" else R_MOD - 1] * n
     Cc = [x * y % R_MOD for x, y in zip(A, B)]
     Q = [1 if i < u else 0 for i in range(n)]
     Q2 = [1 if (i % 8 != 7 and i + 1 < u) else 0 for i in range(n)]

@@ -21,19 +21,23 @@ import numpy as np
 N_GATE_COLS, N_LOOKUP_COLS, N_FIXED, N_TABLE_COLS, N_GATES, TABLE_BITS = 14, 11, 18, 5, 24, 16
 
 
-def build(z, be, k: int, seed: int = 20241008, table_bits: int = TABLE_BITS, census: str = "chip_estimate"):
+def build(z, be, k: int, seed: int = 20241008, table_bits: int = TABLE_BITS, census: str = "chip_estimate", extreme: str | None = None):
     """-> (cs, fixed_columns [(n,4) uint64], assembly, advice_columns [(n,4) uint64]).  census: "chip_estimate" (this function: every column a guess
-    from SURVEY §3.1) or "reference_exact" (build_reference_exact below: the base64 part exactly as the reference configures and assigns it)."""
+    from SURVEY §3.1) or "reference_exact" (build_reference_exact below: the base64 part exactly as the reference configures and assigns it).
+    extreme (chip_estimate, tests of degenerate witnesses; the circuit stays satisfied): "zeros" — every gate block and every unconstrained cell 0, every lookup column the
+    table's row 0; "max" — a = b = c = r - 1 in every block (d = a + b * c is then exactly 0), the unconstrained cells r - 1, every lookup column the table's last row."""
     if census == "reference_exact":
+        assert extreme is None
         return build_reference_exact(z, be, k, seed)
     # "full_chain_x4": BASELINE configs[4] / SURVEY 8d cfg 5 — the full DCAP chain (root -> intermediate -> leaf certificate ECDSA + QE3 + isv_report signatures,
     # several SHA-256) does not exist in the reference (README.md:23-47 is a roadmap); its op-mix is cfg 2's with the advice and lookup counts x 4, synthetic, at k = 21
     assert census in ("chip_estimate", "full_chain_x4"), census
     scale = 4 if census == "full_chain_x4" else 1
-    return _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS * scale, N_LOOKUP_COLS * scale, N_TABLE_COLS + (N_FIXED - N_TABLE_COLS) * scale, N_GATES * scale)
+    return _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS * scale, N_LOOKUP_COLS * scale, N_TABLE_COLS + (N_FIXED - N_TABLE_COLS) * scale, N_GATES * scale, extreme)
 
 
-def _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS, N_LOOKUP_COLS, N_FIXED, N_GATES):
+def _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS, N_LOOKUP_COLS, N_FIXED, N_GATES, extreme=None):
+    assert extreme in (None, "zeros", "max"), extreme
     plonk, F = z.plonk, z.fields
     Advice, Fixed = plonk.Advice, plonk.Fixed
     n = 1 << k
@@ -74,17 +78,20 @@ def _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS, N_LOOKUP_COLS,
     # ---- advice: gate columns (pairs share b) ---------------------------------------------------------------------------
     advice = []
     b_shared = None
+    edge = lambda rows: np.repeat((F.fr_mont(0) if extreme == "zeros" else F.fr_mont(F.R_MOD - 1)).reshape(1, 4), rows, axis=0)
     for c in range(N_GATE_COLS):
         a_, c_ = F.rand_fr_array(rng, nblk), F.rand_fr_array(rng, nblk)
         if c % 2 == 0:
             b_shared = F.rand_fr_array(rng, nblk)
+        if extreme:
+            a_ = c_ = b_shared = edge(nblk)
         da, db, dc = be.to_device(a_), be.to_device(b_shared), be.to_device(c_)
         be.fr_mul_dev(db, dc, dc, nblk)
         be.fr_add_dev(da, dc, dc, nblk)                               # d = a + b*c
         d_ = dc.download((nblk, 4))
         for x in (da, db, dc):
             x.free()
-        col = F.rand_fr_array(rng, n)                                 # cells outside the blocks: unconstrained
+        col = F.rand_fr_array(rng, n) if not extreme else edge(n)     # cells outside the blocks: unconstrained
         blk = col[: 4 * nblk].reshape(nblk, 4, 4)
         blk[:, 0], blk[:, 1], blk[:, 2], blk[:, 3] = a_, b_shared, c_, d_
         advice.append(col)
@@ -94,6 +101,8 @@ def _build_chip_estimate(z, be, k, seed, table_bits, N_GATE_COLS, N_LOOKUP_COLS,
     w_prev = None
     for l in range(N_LOOKUP_COLS):
         w = rng.integers(0, T, size=n)
+        if extreme:
+            w[:] = 0 if extreme == "zeros" else T - 1
         if l == 1:
             w[:half] = w_prev[:half]
         w_prev = w

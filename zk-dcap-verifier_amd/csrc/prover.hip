@@ -888,19 +888,25 @@ struct Proof {
         std::stable_sort(q.begin(), q.end(), [](const Query& a, const Query& b) { return a.open < b.open; });
         return shplonk_create_proof(ctx, mem, tr, q, n, [this](void* poly) { return commit(pk->srs_g, {poly}); });
     }
+    // A commitment to the zero polynomial is the identity, which no transcript can absorb (Transcript::bad_point; halo2's common_point: "cannot write points at infinity
+    // to the transcript").  The proof stops at the end of the phase that committed it and says which one: no byte is returned, so where inside the phase does not matter.
+    int refused(const char* phase) {
+        if (!tr.bad_point) return ZK_OK;
+        return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof: a commitment of the %s phase is the point at infinity (the committed column is zero on every row): "
+                                        "cannot write points at infinity to the transcript", phase);
+    }
     // the phases in halo2's order; the laps are the nine intervals of zk_plonk_last_phase_ms
     int run() {
         PK(validate_and_plan());
         PK(instance_columns());  clk.lap(0);
-        PK(advice_columns());    clk.lap(1);
-        PK(lookups());           clk.lap(2);
-        PK(grand_products());    clk.lap(3);
-        PK(random_polynomial()); clk.lap(4);
+        PK(advice_columns());    PK(refused("advice"));                  clk.lap(1);
+        PK(lookups());           PK(refused("lookup permutation"));      clk.lap(2);
+        PK(grand_products());    PK(refused("grand product"));           clk.lap(3);
+        PK(random_polynomial()); PK(refused("random polynomial"));       clk.lap(4);
         PK(quotient());          clk.lap(5);
-        PK(quotient_pieces());   clk.lap(6);
+        PK(quotient_pieces());   PK(refused("quotient h(X)"));           clk.lap(6);
         PK(evaluations());       clk.lap(7);
-        PK(multi_open());        clk.lap(8);
-        if (tr.bad_point) return ZK_ERR_ARG;                          // a commitment to the zero polynomial under a transcript that cannot encode the identity
+        PK(multi_open());        PK(refused("multi-open"));              clk.lap(8);
         draws.finish();
         *proof_len = tr.out.size();
         if (!proof_out || proof_cap < tr.out.size()) return ZK_ERR_LIMIT;
