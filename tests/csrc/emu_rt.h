@@ -8,6 +8,7 @@
 #include <ucontext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <malloc.h>
 #include <string.h>
 #include <atomic>
 #include <mutex>
@@ -173,7 +174,9 @@ static inline hipError_t hipSetDevice(int) { return 0; }
 static inline hipError_t hipGetLastError() { return 0; }
 inline std::atomic<long> emu_live_device_allocs{0};      // blocks handed out by hipMalloc / hipHostMalloc and not yet freed: the leak check of tests/test_abi_no_throw.py
 static inline hipError_t hipMalloc(void** p, size_t n) { if (posix_memalign(p, 256, n ? n : 256)) return 2; emu_live_device_allocs++; return 0; }
-static inline hipError_t hipFree(void* p) { if (p) emu_live_device_allocs--; free(p); return 0; }
+// a freed block is overwritten before the heap takes it back: a kernel that still reads a table its context has evicted (tests/test_context_history.py) computes
+// garbage here instead of the values the heap happened to leave in place
+static inline hipError_t hipFree(void* p) { if (p) { emu_live_device_allocs--; memset(p, 0xA5, malloc_usable_size(p)); __asm__ __volatile__("" : : "r"(p) : "memory"); } free(p); return 0; }      // (the barrier keeps the store: it is dead to the compiler)
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return 0; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return 0; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }

@@ -78,9 +78,10 @@ def rand_cols(pc_mod, orc, pyref, count, size, seed, kind="uniform"):
     return [pc_mod.column(orc, pyref, size, seed + 7 * i, kind) for i in range(count)]
 
 
-def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_kernels=False, kind="uniform"):
+def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_kernels=False, kind="uniform", evaluator=None):
     """kind: every column (fixed, advice, instance, sigma cosets, grand products, lookup columns, l0 / l_last / l_active_row) is a structured column of that kind
-    (parity_cases.structured_fr) in place of a uniform one; the challenges stay uniform"""
+    (parity_cases.structured_fr) in place of a uniform one; the challenges stay uniform.  evaluator: an ev.Evaluator of `prog` the caller loaded and keeps (several runs
+    of one loaded program); by default the program is loaded here and released at the end"""
     size = 1 << prog.extended_k
     chunk = prog.cs_degree - 2
     n_sets = (len(prog.perm_columns) + chunk - 1) // chunk if prog.perm_columns else 0
@@ -99,8 +100,8 @@ def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_ker
     dev = {k: [be.to_device(c) for c in v] for k, v in cols.items()}
     d_l0, d_ll, d_la = be.to_device(l0), be.to_device(l_last), be.to_device(l_active)
     out = be.alloc(size * 32)
-    e = ev.Evaluator(prog, backend=be)
-    if expect_kernels:                                                 # tests/test_quotient_jit.py: the program must run on kernels generated for it, not on the interpreter
+    e = evaluator if evaluator is not None else ev.Evaluator(prog, backend=be)
+    if expect_kernels:                                                # tests/test_quotient_jit.py: the program must run on kernels generated for it, not on the interpreter
         assert be.quotient_program_kernels(e.handle) >= (2 if expect_kernels is True else int(expect_kernels)), "the program was loaded without generated kernels (tune quot_jit)"
     e.evaluate_h(fixed=dev["fixed"], advice=dev["advice"], instance=dev["instance"], l0=d_l0, l_last=d_ll, l_active_row=d_la,
                  perm_cosets=dev["perm_cosets"], perm_products=dev["perm_products"], lookup_product=dev["lookup_product"],
@@ -154,7 +155,8 @@ def run_case(be, orc, pyref, pc_mod, prog, seed=5, check_cosets=True, expect_ker
         for j in range(lc):
             assert (orc.fr_add(np.ascontiguousarray(h_hi[j::nc]), np.ascontiguousarray(h_lo[j * n:(j + 1) * n])) == want[j::nc]).all(), ("split, extended layout, coset", j)
         hi.free(); lo.free()
-    e.release()
+    if evaluator is None:
+        e.release()
     for v in dev.values():
         for d in v:
             d.free()
