@@ -1024,3 +1024,12 @@ int ntt_pow_tables(zk_ctx* ctx, uint32_t log_n, const u256& omega, const void** 
     return ZK_OK;
 }
 }  // namespace zk
+
+#ifdef ZK_EMU
+// TEST-ONLY (emulator build): the radices plan_passes gives a transform of 2^log_n under the context's tunables (tests/ntt_cases.py restates the plan and is pinned here).
+extern "C" int zk_test_ntt_plan(zk_ctx* ctx, uint32_t log_n, uint32_t radix_log[3], int* passes) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    zk::plan_passes(log_n, ctx->tune, radix_log, passes);
+    return 0;
+}
+#endif
