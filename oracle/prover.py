@@ -14,6 +14,8 @@ Python ints, NTTs are oracle/pyref.py's, the quotient is evaluated from its DEFI
 lookups are permuted with sorted() and a dict, grand products use pow(x, -1, r); only the multi-scalar multiplications go through the C
 oracle (oracle/bn254_oracle.c, halo2's best_multiexp restated).  The circuit description (`cs`: column counts, gate / lookup expression
 trees, equality columns, query lists) is read as DATA, the way oracle/verifier.py reads it.  Sized for k <= 10.
+create_proof_multi is the whole of it — one proof over m circuits, advice in phases, user challenges (the draw and transcript order
+is written out here a second time, nothing is taken from the product's draw plan); create_proof is its m = 1 call without a callback.
 
 Spec points that are this repo's (mirror = oracle, neither checkable against Rust here): vk.transcript_repr (Blake2b of the key's Debug-like
 rendering), the rejection sampler standing in for Fr::random, the order of the random draws.
@@ -118,8 +120,8 @@ def _interpolate(points, evals):
     return coeffs
 
 
-def _eval_expr(e, fx, ad, ins):
-    """Expression::evaluate; fx / ad / ins: (column, rotation) -> int"""
+def _eval_expr(e, fx, ad, ins, ch=()):
+    """Expression::evaluate; fx / ad / ins: (column, rotation) -> int; ch: the user challenges by index (Expression::Challenge(i): degree 0, no query)"""
     t = type(e).__name__
     if t == "Constant":
         return e.value % R
@@ -129,14 +131,16 @@ def _eval_expr(e, fx, ad, ins):
         return ad(e.column, e.rotation)
     if t == "Instance":
         return ins(e.column, e.rotation)
+    if t == "Challenge":
+        return ch[e.index] % R
     if t == "Negated":
-        return -_eval_expr(e.a, fx, ad, ins) % R
+        return -_eval_expr(e.a, fx, ad, ins, ch) % R
     if t == "Sum":
-        return (_eval_expr(e.a, fx, ad, ins) + _eval_expr(e.b, fx, ad, ins)) % R
+        return (_eval_expr(e.a, fx, ad, ins, ch) + _eval_expr(e.b, fx, ad, ins, ch)) % R
     if t == "Product":
-        return _eval_expr(e.a, fx, ad, ins) * _eval_expr(e.b, fx, ad, ins) % R
+        return _eval_expr(e.a, fx, ad, ins, ch) * _eval_expr(e.b, fx, ad, ins, ch) % R
     if t == "Scaled":
-        return _eval_expr(e.a, fx, ad, ins) * e.f % R
+        return _eval_expr(e.a, fx, ad, ins, ch) * e.f % R
     raise TypeError(t)
 
 
@@ -219,6 +223,9 @@ def keygen(params: Params, cs, fixed_columns, copies=()) -> Keys:
     h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
     h.update(repr((k, cs.num_fixed_columns, cs.num_advice_columns, cs.num_instance_columns, len(cs.gates), len(cs.lookups),
                    cs.permutation_columns, cs.degree(), keys.fixed_commitments, keys.permutation_commitments)).encode())
+    phase_of, challenge_phase = _phase_lists(cs)
+    if any(phase_of) or challenge_phase:                             # a key with later phases or user challenges renders them too; single-phase keys keep their bytes
+        h.update(repr(("phases", phase_of, challenge_phase)).encode())
     keys.transcript_repr = int.from_bytes(h.digest(), "little") % R
     keys.fixed_polys = [_intt(c, k) for c in keys.fixed_values]
     keys.sigma_polys = [_intt(c, k) for c in keys.sigma_values]
@@ -262,223 +269,298 @@ def _permute_expression_pair(inp, tab, usable, blind_in, blind_tab):
     return a + list(blind_in), s + list(blind_tab)
 
 
+def _phase_lists(cs):
+    """(cs.advice_column_phase padded with phase 0, cs.challenge_phase), read as data: a constraint system without them is single-phase"""
+    ap = list(getattr(cs, "advice_column_phase", None) or [])
+    ap += [0] * (cs.num_advice_columns - len(ap))
+    return ap, list(getattr(cs, "challenge_phase", None) or [])
+
+
 def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.Generator, require_satisfied: bool = True) -> bytes:
-    """advice: cs.num_advice_columns lists of n canonical ints (rows past the usable ones are overwritten with blinding); instances: lists of
-    canonical ints.  Returns the proof bytes (Blake2b transcript).  require_satisfied = False: behave as halo2 does on a witness that violates a gate —
-    no check, extended_to_coeff silently truncates h(X) to (d-1) n coefficients (poly/domain.rs) — instead of stopping (differential tests on random circuits).
-    Every Fr::random of halo2's provers is drawn in place, including the Blind each commitment draws (`blind()` below: drawn and dropped, as KZG does)."""
+    """One circuit, every column in the caller's hands: create_proof_multi over [advice], [instances] without a callback.  advice: cs.num_advice_columns lists of n
+    canonical ints (rows past the usable ones are overwritten with blinding); instances: lists of canonical ints."""
+    return create_proof_multi(params, keys, [advice], [instances], rng, require_satisfied=require_satisfied)
+
+
+def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng: np.random.Generator, next_phase=None, require_satisfied: bool = True,
+                       challenges_out: list | None = None) -> bytes:
+    """halo2's create_proof(params, pk, &[c0, c1, ..], &[inst0, inst1, ..], rng, transcript): ONE proof over m = len(advices) circuits that share the key, their advice
+    committed in the phases cs.advice_column_phase names, cs.challenge_phase's user challenges squeezed between them.
+    advices[c]: circuit c's cs.num_advice_columns lists of n canonical ints; the entries of later-phase columns are ignored (None will do): once the challenges of phase
+    p are squeezed, next_phase(p + 1, challenges, c) -> {column: n canonical ints} is asked for every column of phase p + 1 of circuit c (challenges: one int per
+    cs.challenge_phase entry, 0 where not squeezed yet).  instances_list[c]: circuit c's lists of canonical ints.  Returns the proof bytes (Blake2b transcript).
+    require_satisfied = False: behave as halo2 does on a witness that violates a gate — no check, extended_to_coeff silently truncates h(X) to (d-1) n coefficients
+    (poly/domain.rs) — instead of stopping (differential tests on random circuits).  challenges_out receives every value squeezed: the user challenges in index order,
+    then theta, beta, gamma, y, x, SHPLONK's y, v, u.
+    Every Fr::random of halo2's provers is drawn in place, including the Blind each commitment draws (`blind()` below: drawn and dropped, as KZG does).  Wherever halo2
+    loops over the circuits it does so in order 0 .. m-1 and finishes circuit c before circuit c + 1; the vanishing argument, the fixed and the sigma columns exist once."""
 
     def blind(times=1):                                              # `Blind(Scheme::Scalar::random(&mut rng))`: the stream advances, the value is unused under KZG
         for _ in range(times):
             rand_fr(rng, 1)
     cs, k, n = keys.cs, params.k, params.n
+    m = len(advices)
+    assert m >= 1 and len(instances_list) == m
+    circuits = range(m)
     w = p.omega(k)
     ek = _extended_k(cs, k)
     en, step = 1 << ek, 1 << (ek - k)
     bf = cs.blinding_factors()
     usable = n - (bf + 1)
-    L = len(cs.lookups)
+    n_adv, L = cs.num_advice_columns, len(cs.lookups)
     tr = _Writer()
-    # 1 ---------------------------------------------------------------------------------------------------------------------------------------
+    # 1: the key, then every circuit's instance values ------------------------------------------------------------------------------------------
     tr.common_scalar(keys.transcript_repr)
-    inst_values = []
-    for col in instances:
-        for v in col:
-            tr.common_scalar(v)
-        inst_values.append([int(v) % R for v in col] + [0] * (n - len(col)))
-    # 2 ---------------------------------------------------------------------------------------------------------------------------------------
-    adv_values = []
-    for col in advice:
-        col = [int(v) % R for v in col]
-        assert len(col) == n
-        col[usable:] = rand_fr(rng, n - usable)
-        adv_values.append(col)
-    blind(len(adv_values))                                           # plonk/prover.rs: `let blinds: Vec<_> = advice_values.iter().map(|_| Blind(random)).collect()`
-    for col in adv_values:
-        tr.write_point(params.commit_lagrange(col))
-    # 3 ---------------------------------------------------------------------------------------------------------------------------------------
+    inst_values = []                                                 # [circuit][column]
+    for instances in instances_list:
+        assert len(instances) == cs.num_instance_columns
+        per = []
+        for col in instances:
+            for v in col:
+                tr.common_scalar(v)
+            per.append([int(v) % R for v in col] + [0] * (n - len(col)))
+        inst_values.append(per)
+    # 2: advice, phase by phase; inside a phase circuit by circuit ----------------------------------------------------------------------------------
+    phase_of, challenge_phase = _phase_lists(cs)
+    last_phase = max(phase_of, default=0)
+    challenges = [0] * len(challenge_phase)
+    given = [list(a) for a in advices]                               # [circuit][column] as the caller's synthesis made them
+    assert all(len(a) == n_adv for a in given)
+    adv_values = [[None] * n_adv for _ in circuits]
+    for phase in range(last_phase + 1):
+        cols = [i for i in range(n_adv) if phase_of[i] == phase]
+        for c in circuits:
+            for i in cols:
+                col = [int(v) % R for v in given[c][i]]
+                assert len(col) == n
+                col[usable:] = rand_fr(rng, n - usable)
+                adv_values[c][i] = col
+            blind(len(cols))                                         # plonk/prover.rs: `let blinds: Vec<_> = advice_values.iter().map(|_| Blind(random)).collect()`
+            for i in cols:
+                tr.write_point(params.commit_lagrange(adv_values[c][i]))
+        for i, ph in enumerate(challenge_phase):                     # after the last circuit of the phase: its challenges, ascending index
+            if ph == phase:
+                challenges[i] = tr.squeeze()
+        if phase < last_phase:                                       # the caller's synthesis of the next phase, with what is squeezed so far
+            for c in circuits:
+                for i, col in next_phase(phase + 1, list(challenges), c).items():
+                    assert phase_of[i] == phase + 1, (i, phase + 1)
+                    given[c][i] = col
+    # 3: lookups — per circuit, per lookup ----------------------------------------------------------------------------------------------------------
     theta = tr.squeeze()
-    lag = {ADVICE: adv_values, FIXED: keys.fixed_values, INSTANCE: inst_values}
 
-    def compress(exprs):
+    def compress(c, exprs):
         out = []
         for i in range(n):
-            fx = lambda c, r: keys.fixed_values[c][(i + r) % n]
-            ad = lambda c, r: adv_values[c][(i + r) % n]
-            ins = lambda c, r: inst_values[c][(i + r) % n]
+            fx = lambda col, r: keys.fixed_values[col][(i + r) % n]
+            ad = lambda col, r: adv_values[c][col][(i + r) % n]
+            ins = lambda col, r: inst_values[c][col][(i + r) % n]
             acc = 0
             for e in exprs:
-                acc = (acc * theta + _eval_expr(e, fx, ad, ins)) % R
+                acc = (acc * theta + _eval_expr(e, fx, ad, ins, challenges)) % R
             out.append(acc)
         return out
-    compressed = [(compress(lk.input_expressions), compress(lk.table_expressions)) for lk in cs.lookups]
+    compressed = [[(compress(c, lk.input_expressions), compress(c, lk.table_expressions)) for lk in cs.lookups] for c in circuits]
     permuted = []                                                    # lookup/prover.rs commit_permuted, lookup by lookup: permute_expression_pair extends the input
-    for cin_, ctab_ in compressed:                                   # then the table with random rows, commit_values draws one Blind per commitment
-        bi_ = rand_fr(rng, bf + 1)
-        bt_ = rand_fr(rng, bf + 1)
-        permuted.append(_permute_expression_pair(cin_, ctab_, usable, bi_, bt_))
-        blind(2)
-    for a_, s_ in permuted:
-        tr.write_point(params.commit_lagrange(a_))
-        tr.write_point(params.commit_lagrange(s_))
-    # 4 ---------------------------------------------------------------------------------------------------------------------------------------
+    for c in circuits:                                               # then the table with random rows, commit_values draws one Blind per commitment
+        per = []
+        for cin_, ctab_ in compressed[c]:
+            bi_ = rand_fr(rng, bf + 1)
+            bt_ = rand_fr(rng, bf + 1)
+            per.append(_permute_expression_pair(cin_, ctab_, usable, bi_, bt_))
+            blind(2)
+        permuted.append(per)
+    for c in circuits:
+        for a_, s_ in permuted[c]:
+            tr.write_point(params.commit_lagrange(a_))
+            tr.write_point(params.commit_lagrange(s_))
+    # 4: grand products — every circuit's permutation sets, then every circuit's lookup products; the vanishing argument once -----------------------------
     beta, gamma = tr.squeeze(), tr.squeeze()
-    perm_cols = [lag[t][i] for t, i in cs.permutation_columns]
+    column_values = lambda c: {ADVICE: adv_values[c], FIXED: keys.fixed_values, INSTANCE: inst_values[c]}
+    n_perm = len(cs.permutation_columns)
     chunk = cs.permutation_chunk_len()
-    n_sets = (len(perm_cols) + chunk - 1) // chunk if perm_cols else 0
+    n_sets = (n_perm + chunk - 1) // chunk if n_perm else 0
     perm_blind, lookup_blind = [], []
-    for _ in range(n_sets):                                          # permutation/prover.rs: the set's blinding rows, then its Blind
-        perm_blind.append(rand_fr(rng, bf))
-        blind()
-    for _ in range(L):                                               # lookup/prover.rs commit_product: the same per lookup
-        lookup_blind.append(rand_fr(rng, bf))
-        blind()
+    for c in circuits:                                               # permutation/prover.rs: the set's blinding rows, then its Blind
+        perm_blind.append([])
+        for _ in range(n_sets):
+            perm_blind[c].append(rand_fr(rng, bf))
+            blind()
+    for c in circuits:                                               # lookup/prover.rs commit_product: the same per lookup
+        lookup_blind.append([])
+        for _ in range(L):
+            lookup_blind[c].append(rand_fr(rng, bf))
+            blind()
     random_poly = rand_fr(rng, n)                                    # vanishing/prover.rs commit: n coefficients, one Blind; construct: one Blind per piece of h(X)
     blind(1 + (cs.degree() - 1))
     wp = [pow(w, i, R) for i in range(n)]
-    zs, last_z = [], 1
-    for s in range(n_sets):
-        z = [last_z]
-        for i in range(n - 1):
-            num = den = 1
-            for j in range(s * chunk, min((s + 1) * chunk, len(perm_cols))):
-                v = perm_cols[j][i]
-                num = num * (v + pow(p.DELTA, j, R) * beta % R * wp[i] + gamma) % R
-                den = den * (v + beta * keys.sigma_values[j][i] + gamma) % R
-            z.append(z[-1] * num % R * pow(den, -1, R) % R)
-        z[n - bf:] = perm_blind[s]
-        last_z = z[n - (bf + 1)]
-        zs.append(z)
-    lzs = []
-    for j, ((cin, ctab), (pin, ptab)) in enumerate(zip(compressed, permuted)):
-        z = [1]
-        for i in range(n - 1):
-            num = (cin[i] + beta) * (ctab[i] + gamma) % R
-            den = (pin[i] + beta) * (ptab[i] + gamma) % R
-            z.append(z[-1] * num % R * pow(den, -1, R) % R)
-        z[n - bf:] = lookup_blind[j]
-        lzs.append(z)
-    for z in zs + lzs:
-        tr.write_point(params.commit_lagrange(z))
+    zs, lzs = [], []                                                 # [circuit][set], [circuit][lookup]
+    for c in circuits:
+        perm_cols = [column_values(c)[t][i] for t, i in cs.permutation_columns]
+        per, last_z = [], 1                                          # (every circuit's first set starts from 1)
+        for s in range(n_sets):
+            z = [last_z]
+            for i in range(n - 1):
+                num = den = 1
+                for j in range(s * chunk, min((s + 1) * chunk, n_perm)):
+                    v = perm_cols[j][i]
+                    num = num * (v + pow(p.DELTA, j, R) * beta % R * wp[i] + gamma) % R
+                    den = den * (v + beta * keys.sigma_values[j][i] + gamma) % R
+                z.append(z[-1] * num % R * pow(den, -1, R) % R)
+            z[n - bf:] = perm_blind[c][s]
+            last_z = z[n - (bf + 1)]
+            per.append(z)
+        zs.append(per)
+        per = []
+        for j, ((cin, ctab), (pin, ptab)) in enumerate(zip(compressed[c], permuted[c])):
+            z = [1]
+            for i in range(n - 1):
+                num = (cin[i] + beta) * (ctab[i] + gamma) % R
+                den = (pin[i] + beta) * (ptab[i] + gamma) % R
+                z.append(z[-1] * num % R * pow(den, -1, R) % R)
+            z[n - bf:] = lookup_blind[c][j]
+            per.append(z)
+        lzs.append(per)
+    for c in circuits:
+        for z in zs[c]:
+            tr.write_point(params.commit_lagrange(z))
+    for c in circuits:
+        for z in lzs[c]:
+            tr.write_point(params.commit_lagrange(z))
     # 5 ---------------------------------------------------------------------------------------------------------------------------------------
     tr.write_point(params.commit(random_poly))
-    # 6 ---------------------------------------------------------------------------------------------------------------------------------------
+    # 6: the numerator — ONE Horner chain in y over (circuit 0: gates, permutation, lookups), (circuit 1: ..), .. (evaluate_h does not start again between circuits) ------
     y = tr.squeeze()
-    adv_polys = [_intt(c, k) for c in adv_values]
-    inst_polys = [_intt(c, k) for c in inst_values]
-    z_polys = [_intt(c, k) for c in zs]
-    lz_polys = [_intt(c, k) for c in lzs]
-    perm_polys = [(_intt(a_, k), _intt(s_, k)) for a_, s_ in permuted]
-    ce = lambda c: _coset_evals(c, k, ek)
-    A, F, I = [ce(c) for c in adv_polys], [ce(c) for c in keys.fixed_polys], [ce(c) for c in inst_polys]
-    SG = [ce(c) for c in keys.sigma_polys]
-    Z, LZ = [ce(c) for c in z_polys], [ce(c) for c in lz_polys]
-    PA, PS = [ce(a_) for a_, _ in perm_polys], [ce(s_) for _, s_ in perm_polys]
+    adv_polys = [[_intt(col, k) for col in adv_values[c]] for c in circuits]
+    inst_polys = [[_intt(col, k) for col in inst_values[c]] for c in circuits]
+    z_polys = [[_intt(z, k) for z in zs[c]] for c in circuits]
+    lz_polys = [[_intt(z, k) for z in lzs[c]] for c in circuits]
+    perm_polys = [[(_intt(a_, k), _intt(s_, k)) for a_, s_ in permuted[c]] for c in circuits]
+    ce = lambda coeffs: _coset_evals(coeffs, k, ek)
+    F, SG = [ce(col) for col in keys.fixed_polys], [ce(col) for col in keys.sigma_polys]
+    A = [[ce(col) for col in adv_polys[c]] for c in circuits]
+    I = [[ce(col) for col in inst_polys[c]] for c in circuits]
+    Z, LZ = [[ce(z) for z in z_polys[c]] for c in circuits], [[ce(z) for z in lz_polys[c]] for c in circuits]
+    PA, PS = [[ce(a_) for a_, _ in perm_polys[c]] for c in circuits], [[ce(s_) for _, s_ in perm_polys[c]] for c in circuits]
     unit = lambda rows: ce(_intt([1 if i in rows else 0 for i in range(n)], k))
     l0, l_last = unit({0}), unit({n - bf - 1})
     l_active = unit(set(range(n - bf - 1)))
     ext_w = pow(p.ROOT_OF_UNITY, 1 << (p.S - ek), R)
-    ext_cols = {ADVICE: A, FIXED: F, INSTANCE: I}
     last_rot = -(bf + 1)
     h_ext = []
     zeta_n = pow(p.ZETA, n, R)
     ext_w_n = pow(ext_w, n, R)
     for idx in range(en):
         at = lambda col, r: col[(idx + r * step) % en]
-        fx = lambda c, r: at(F[c], r)
-        ad = lambda c, r: at(A[c], r)
-        ins = lambda c, r: at(I[c], r)
         X = p.ZETA * pow(ext_w, idx, R) % R
         value = 0
-        for g in cs.gates:
-            value = (value * y + _eval_expr(g, fx, ad, ins)) % R
-        if n_sets:
-            value = (value * y + (1 - Z[0][idx]) * l0[idx]) % R
-            zl = Z[-1][idx]
-            value = (value * y + (zl * zl - zl) * l_last[idx]) % R
-            for s in range(1, n_sets):
-                value = (value * y + (Z[s][idx] - at(Z[s - 1], last_rot)) * l0[idx]) % R
-            for s in range(n_sets):
-                left, right = at(Z[s], 1), Z[s][idx]
-                for j in range(s * chunk, min((s + 1) * chunk, len(perm_cols))):
-                    t, ci = cs.permutation_columns[j]
-                    v = ext_cols[t][ci][idx]
-                    left = left * (v + beta * SG[j][idx] + gamma) % R
-                    right = right * (v + pow(p.DELTA, j, R) * beta % R * X + gamma) % R
+        for c in circuits:
+            fx = lambda col, r: at(F[col], r)
+            ad = lambda col, r: at(A[c][col], r)
+            ins = lambda col, r: at(I[c][col], r)
+            ext_cols = {ADVICE: A[c], FIXED: F, INSTANCE: I[c]}
+            for g in cs.gates:
+                value = (value * y + _eval_expr(g, fx, ad, ins, challenges)) % R
+            if n_sets:
+                Zc = Z[c]
+                value = (value * y + (1 - Zc[0][idx]) * l0[idx]) % R
+                zl = Zc[-1][idx]
+                value = (value * y + (zl * zl - zl) * l_last[idx]) % R
+                for s in range(1, n_sets):
+                    value = (value * y + (Zc[s][idx] - at(Zc[s - 1], last_rot)) * l0[idx]) % R
+                for s in range(n_sets):
+                    left, right = at(Zc[s], 1), Zc[s][idx]
+                    for j in range(s * chunk, min((s + 1) * chunk, n_perm)):
+                        t, ci = cs.permutation_columns[j]
+                        v = ext_cols[t][ci][idx]
+                        left = left * (v + beta * SG[j][idx] + gamma) % R
+                        right = right * (v + pow(p.DELTA, j, R) * beta % R * X + gamma) % R
+                    value = (value * y + (left - right) * l_active[idx]) % R
+            for j, lk in enumerate(cs.lookups):
+                def comp(es):
+                    acc = 0
+                    for e in es:
+                        acc = (acc * theta + _eval_expr(e, fx, ad, ins, challenges)) % R
+                    return acc
+                z_, a_, s_ = LZ[c][j][idx], PA[c][j][idx], PS[c][j][idx]
+                value = (value * y + (1 - z_) * l0[idx]) % R
+                value = (value * y + (z_ * z_ - z_) * l_last[idx]) % R
+                left = at(LZ[c][j], 1) * (a_ + beta) % R * (s_ + gamma) % R
+                right = z_ * (comp(lk.input_expressions) + beta) % R * (comp(lk.table_expressions) + gamma) % R
                 value = (value * y + (left - right) * l_active[idx]) % R
-        for j, lk in enumerate(cs.lookups):
-            def comp(es):
-                acc = 0
-                for e in es:
-                    acc = (acc * theta + _eval_expr(e, fx, ad, ins)) % R
-                return acc
-            z_, a_, s_ = LZ[j][idx], PA[j][idx], PS[j][idx]
-            value = (value * y + (1 - z_) * l0[idx]) % R
-            value = (value * y + (z_ * z_ - z_) * l_last[idx]) % R
-            left = at(LZ[j], 1) * (a_ + beta) % R * (s_ + gamma) % R
-            right = z_ * (comp(lk.input_expressions) + beta) % R * (comp(lk.table_expressions) + gamma) % R
-            value = (value * y + (left - right) * l_active[idx]) % R
-            value = (value * y + (a_ - s_) * l0[idx]) % R
-            value = (value * y + (a_ - s_) * (a_ - at(PA[j], -1)) % R * l_active[idx]) % R
+                value = (value * y + (a_ - s_) * l0[idx]) % R
+                value = (value * y + (a_ - s_) * (a_ - at(PA[c][j], -1)) % R * l_active[idx]) % R
         t_inv = pow((zeta_n * pow(ext_w_n, idx, R) - 1) % R, -1, R)           # 1 / (X^n - 1) on the coset
         h_ext.append(value * t_inv % R)
     # 7: back to coefficients (extended_to_coeff), split, commit -------------------------------------------------------------------------------
     en_inv = pow(en, -1, R)
     hc = [v * en_inv % R for v in p.ntt_fast(h_ext, pow(ext_w, -1, R))]
     zinv = pow(p.ZETA, -1, R)
-    hc = [c * pow(zinv, i % 3, R) % R for i, c in enumerate(hc)]
+    hc = [c_ * pow(zinv, i % 3, R) % R for i, c_ in enumerate(hc)]
     n_pieces = cs.degree() - 1
     assert not (require_satisfied and any(hc[n_pieces * n:])), "the witness does not satisfy the circuit: h(X) has degree >= (d-1) n"
     pieces = [hc[i * n:(i + 1) * n] for i in range(n_pieces)]
     for pc in pieces:
         tr.write_point(params.commit(pc))
-    # 8 ---------------------------------------------------------------------------------------------------------------------------------------
+    # 8: evaluations — advice per circuit; fixed, the random polynomial, sigma once; permutation per circuit; lookups per circuit -------------------------
     x = tr.squeeze()
     xn = pow(x, n, R)
     rot = lambda r: x * pow(w, r % n, R) % R
-    h_poly = [sum(pow(xn, i, R) * pieces[i][c] for i in range(n_pieces)) % R for c in range(n)]
+    h_poly = [sum(pow(xn, i, R) * pieces[i][c_] for i in range(n_pieces)) % R for c_ in range(n)]
     x_last = rot(last_rot)
     Q = []                                                             # (key, poly, point) in evaluation order
-    for c, r in cs.advice_queries():
-        Q.append((("adv", c), adv_polys[c], rot(r)))
-    for c, r in cs.fixed_queries():
-        Q.append((("fix", c), keys.fixed_polys[c], rot(r)))
+    for c in circuits:
+        for col, r in cs.advice_queries():
+            Q.append((("adv", c, col), adv_polys[c][col], rot(r)))
+    for col, r in cs.fixed_queries():
+        Q.append((("fix", col), keys.fixed_polys[col], rot(r)))
     Q.append((("rand",), random_poly, x))
     for j, sp in enumerate(keys.sigma_polys):
         Q.append((("sig", j), sp, x))
-    for i, zp in enumerate(z_polys):
-        Q.append((("pz", i), zp, x))
-        Q.append((("pz", i), zp, rot(1)))
-        if i + 1 < len(z_polys):
-            Q.append((("pz", i), zp, x_last))
-    for j in range(L):
-        Q.append((("lz", j), lz_polys[j], x))
-        Q.append((("lz", j), lz_polys[j], rot(1)))
-        Q.append((("la", j), perm_polys[j][0], x))
-        Q.append((("la", j), perm_polys[j][0], rot(-1)))
-        Q.append((("ls", j), perm_polys[j][1], x))
+    for c in circuits:
+        for i, zp in enumerate(z_polys[c]):
+            Q.append((("pz", c, i), zp, x))
+            Q.append((("pz", c, i), zp, rot(1)))
+            if i + 1 < n_sets:
+                Q.append((("pz", c, i), zp, x_last))
+    for c in circuits:
+        for j in range(L):
+            Q.append((("lz", c, j), lz_polys[c][j], x))
+            Q.append((("lz", c, j), lz_polys[c][j], rot(1)))
+            Q.append((("la", c, j), perm_polys[c][j][0], x))
+            Q.append((("la", c, j), perm_polys[c][j][0], rot(-1)))
+            Q.append((("ls", c, j), perm_polys[c][j][1], x))
     Q.append((("h",), h_poly, x))
     evals = [_poly_eval(poly, pt) for _, poly, pt in Q]
     for e in evals[:-1]:
         tr.write_scalar(e)
-    # 9: ProverSHPLONK — queries in the multi-open order -------------------------------------------------------------------------------------------
+    # 9: ProverSHPLONK — queries in the multi-open order: per circuit its advice, permutation and lookup queries; then fixed, sigma, h and the random polynomial once ----
     it = iter([(key, poly, pt, e) for (key, poly, pt), e in zip(Q, evals)])
     take = lambda: next(it)
-    q_adv = [take() for _ in cs.advice_queries()]
+    q_adv = [[take() for _ in cs.advice_queries()] for _ in circuits]
     q_fix = [take() for _ in cs.fixed_queries()]
     q_rand = take()
     q_sig = [take() for _ in keys.sigma_polys]
-    q_pa, q_pl = [], []
-    for i in range(len(z_polys)):
-        q_pa += [take(), take()]
-        if i + 1 < len(z_polys):
-            q_pl.append(take())
+    q_perm = []
+    for c in circuits:
+        q_pa, q_pl = [], []
+        for i in range(n_sets):
+            q_pa += [take(), take()]
+            if i + 1 < n_sets:
+                q_pl.append(take())
+        q_perm.append(q_pa + list(reversed(q_pl)))
     q_lk = []
-    for _ in range(L):
-        pz, pzn, pa, pai, ps = take(), take(), take(), take(), take()
-        q_lk += [pz, pa, ps, pai, pzn]
+    for c in circuits:
+        per = []
+        for _ in range(L):
+            pz, pzn, pa, pai, ps = take(), take(), take(), take(), take()
+            per += [pz, pa, ps, pai, pzn]
+        q_lk.append(per)
     q_h = take()
-    queries = q_adv + q_pa + list(reversed(q_pl)) + q_lk + q_fix + q_sig + [q_h, q_rand]
+    queries = []
+    for c in circuits:
+        queries += q_adv[c] + q_perm[c] + q_lk[c]
+    queries += q_fix + q_sig + [q_h, q_rand]
     yy = tr.squeeze()
     super_points = sorted({q[2] for q in queries})
     order, info = [], {}
@@ -497,7 +579,7 @@ def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.G
         else:
             sets.append((pts, [key]))
     v = tr.squeeze()
-    padn = lambda c: list(c) + [0] * (n - len(c))
+    padn = lambda coeffs: list(coeffs) + [0] * (n - len(coeffs))
     quotients, low = [], []
     for pts, ks in sets:
         acc, ypow, rs = [0] * n, 1, []
@@ -512,7 +594,7 @@ def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.G
         for pt in pts:                                                 # exact division by the set's vanishing polynomial
             acc = _kate_division(acc, pt)
         quotients.append(padn(acc))
-    h_x = [sum(pow(v, i, R) * q[c] for i, q in enumerate(quotients)) % R for c in range(n)]
+    h_x = [sum(pow(v, i, R) * q[c_] for i, q in enumerate(quotients)) % R for c_ in range(n)]
     tr.write_point(params.commit(h_x))
     u = tr.squeeze()
     vanish = lambda roots, z_: __import__("functools").reduce(lambda a_, r_: a_ * (z_ - r_) % R, roots, 1)
@@ -524,11 +606,15 @@ def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.G
         for key, r_x in zip(ks, low[i]):
             wgt = pow(v, i, R) * z_diffs[i] % R * ypow % R
             poly = padn(info[key]["poly"])
-            for c in range(n):
-                lx[c] = (lx[c] + wgt * poly[c]) % R
+            for c_ in range(n):
+                lx[c_] = (lx[c_] + wgt * poly[c_]) % R
             lx[0] = (lx[0] - wgt * _poly_eval(r_x, u)) % R
             ypow = ypow * yy % R
     zt = vanish(super_points, u)
-    lx = [(c - zt * hv) % R * z0_inv % R for c, hv in zip(lx, h_x)]
+    lx = [(c_ - zt * hv) % R * z0_inv % R for c_, hv in zip(lx, h_x)]
     tr.write_point(params.commit(padn(_kate_division(lx, u))))
+    if challenges_out is not None:
+        challenges_out.extend(challenges + [theta, beta, gamma, y, x, yy, v, u])
     return bytes(tr.out)
+
+

@@ -83,6 +83,7 @@ def _rlc_circuit(k, order, m, name, single_phase=False):
     T2 = [rows[u - 1 - r][1] if r < u else 0 for r in range(n)]
     fixed = [[1] + [0] * (n - 1), [1 if r + 1 < u else 0 for r in range(n)], T1, T2]
     asm = plonk.Assembly(cs, k)
+    asm.copies = []                                                   # logged for the independent CPU prover (oracle/prover.py)
     asm.copy((ADVICE, ia, 0), (ADVICE, iacc, 0))
     asm.copy((ADVICE, iacc, 3), (ADVICE, iacc2, 3))
     asm.copy((ADVICE, iacc2, 10), (ADVICE, iacc, 10))
@@ -146,6 +147,7 @@ def case_b(k=6):
     assert cs.degree() == 5 and cs.phases() == [0, 1, 2] and cs.challenge_phase == [0, 1, 1, 2]
     fixed = [[1 if r < u else 0 for r in range(n)]]
     asm = plonk.Assembly(cs, k)
+    asm.copies = []                                                   # logged for the independent CPU prover (oracle/prover.py)
     asm.copy((ADVICE, idd, 2), (ADVICE, ie, 2))
     asm.copy((ADVICE, ie, 9), (ADVICE, idd, 9))
     A = [int(v) for v in np.random.default_rng(200).integers(1, 1 << 40, n)]

@@ -375,8 +375,8 @@ def toy_case(k, extreme=None):
 
 
 def _two_circuits(ring, k):
-    """one proof over two circuits of the toy key: circuit 0 structured (b = c = 0 on every row, both instances 0), circuit 1 the usual witness.  The twin and the oracle are
-    single-circuit: they pin the one-circuit form of the same entry point, and circuit 0's advice commitments, which open the two-circuit proof (its draws come first);
+    """one proof over two circuits of the toy key: circuit 0 structured (b = c = 0 on every row, both instances 0), circuit 1 the usual witness.  The twin is single-circuit
+    (the whole two-circuit proof against the oracle's create_proof_multi: tests/test_oracle_multi_phased.py): twin and oracle pin the one-circuit form of the same entry point, and circuit 0's advice commitments, which open the two-circuit proof (its draws come first);
     the m-circuit verifier accepts the whole and holds it to both statements"""
     circ, (adv0, inst0) = toy_case(k, "zero_b")
     adv1, inst1 = circ["advice"], circ["instances"]

@@ -4,6 +4,8 @@ definition, MSMs on the C oracle — no product code, no kernel emulator):
     toy_proof_k6_seed7.bin     the toy circuit of tests/test_create_proof.py, k = 6, np.random.default_rng(7)
     sgx_shaped_k8_seed3.bin    the sgx_dcap_verifier-shaped circuit (tools/sgx_shaped_circuit.py: 25 advice, 11 lookups, 16 equality columns), k = 8, rng 3
     reference_exact_k9_seed3.bin  census B of the same tool (the reference's base64 sub-circuit built exactly + chip estimate), k = 9, rng 3
+    toy_m2_k6_seed5.bin        ONE proof over two witnesses of the toy key (test_multi_circuit.toy_witness(6, s=c, t=2c), c = 0, 1), rng 5
+    phased_{A,B,D}_k6_seed5.bin   tests/phased_cases.py: two advice phases and a challenge (A), three phases and four challenges (B), A over two circuits (D), rng 5
 The Fr::random draws follow halo2_proofs v2023_01_20 (incl. the Blind of every commitment).  All with the SRS trapdoor TAU of the tests.  The GPU prover (and the emulated kernels) must emit exactly these bytes, and the pure-Python
 verifier must accept them.  They are NOT outputs of the reference (no Rust toolchain here; the reference holds no stack-A proof): they replace the
 round-1 goldens, which the emulator build of the product's own kernels had produced."""
@@ -76,6 +78,16 @@ def main():
         out = os.path.join(ROOT, "tests", "golden", name)
         open(out, "wb").write(proof)
         print("wrote", out, len(proof), "bytes (CPU prover, accepted by verify_proof)")
+    # proofs over several circuits and phased proofs (create_proof_multi): the cases of tests/multi_phase_cases.py, accepted by the test-side m-circuit / phased verifiers
+    import multi_circuit_verifier as mv
+    import multi_phase_cases as mp
+    import phased_verifier as pv
+    for name, build in mp.GOLDENS:
+        (proof, _, keys), cs, insts, phased = build()
+        assert (pv.verify_proof_phased if phased else mv.verify_proof_multi)(keys, mp.TAU, insts, proof) is True, name
+        out = os.path.join(ROOT, "tests", "golden", name)
+        open(out, "wb").write(proof)
+        print("wrote", out, len(proof), "bytes (CPU prover over %d circuit(s), accepted by the test-side verifier)" % len(insts))
 
 
 if __name__ == "__main__":
