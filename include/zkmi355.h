@@ -224,6 +224,15 @@ int zk_kate_division_dev(zk_ctx* ctx, const void* a_dev, size_t n, const void* b
  * out[i] = sum_j scalars[j] * polys[j][i], i < n, in one pass.  polys: HOST array of `count` DEVICE polynomials (n coefficients each);
  * scalars: HOST count x 32 B; out_dev: DEVICE n x 32 B (may alias one of the inputs). */
 int zk_fr_lincomb_dev(zk_ctx* ctx, const void* const* polys_dev, const void* scalars, size_t count, size_t n, void* out_dev);
+/* halo2_proofs src/poly/kzg/multiopen/gwc/prover.rs — the `poly_batch = poly_batch * v + query.poly` folds of ProverGWC::create_proof, all opening points at once:
+ * `count` independent combinations in ONE launch.  Combination p is over polys[offsets[p] .. offsets[p+1]) with the matching scalars (offsets: HOST, count + 1
+ * entries, offsets[0] = 0, ascending; the lists are ragged and a polynomial may stand in several of them), outs[p]: DEVICE n x 32 B.  Same arithmetic as
+ * zk_fr_lincomb_dev, which is the count = 1 case of the same kernel.  ZK_ERR_ARG: a NULL entry, an empty list, an outs[p] that is also an input or another output. */
+int zk_fr_lincomb_batch_dev(zk_ctx* ctx, const void* const* polys, const void* scalars, const uint32_t* offsets, size_t count, size_t n, void* const* outs);
+/* ... and its `kate_division(&poly_batch, z)` per point: `count` divisions in the three launches of one, q_dev[c] = (a_dev[c](X) - a_dev[c](points[c])) / (X - points[c]).
+ * a_dev / q_dev: HOST arrays of DEVICE columns (n coefficients in, n - 1 out; the same a may be divided by several points), points: HOST count x 32 B.
+ * 2 <= n <= 2^27 as for the single call.  ZK_ERR_ARG: a NULL entry, a q_dev[c] that is also an input or another quotient. */
+int zk_kate_division_batch_dev(zk_ctx* ctx, const void* const* a_dev, size_t count, size_t n, const void* points, void* const* q_dev);
 
 /* ---- quotient: replaces plonk::evaluation::Evaluator::evaluate_h ---------------------------- *
  * halo2_proofs src/plonk/evaluation.rs.  The compiled GraphEvaluator of a proving key is uploaded
@@ -502,9 +511,22 @@ int zk_plonk_prove_phased(zk_ctx* ctx, uint64_t pk, uint32_t n_circuits, const v
                           const uint32_t* instance_lens, zk_phase_fn next_phase, void* next_phase_user, zk_rng_fn rng, void* rng_user,
                           void* proof_out, size_t proof_cap, size_t* proof_len);
 /* what the calling thread's last proof (any zk_plonk_create_proof* / zk_plonk_prove*) squeezed, canonical 32-byte little endian: the user challenges in index order,
- * then theta, beta, gamma, y, x and SHPLONK's y, v, u — for a caller that replays the transcript and compares.  *n = their number (n_challenges + 8; fewer after a
- * proof that failed early); ZK_ERR_LIMIT when cap (in bytes) is too small, *n still set. */
+ * then theta, beta, gamma, y, x and SHPLONK's y, v, u (GWC's v) — for a caller that replays the transcript and compares.  *n = their number (n_challenges + 8, with
+ * GWC n_challenges + 6; fewer after a proof that failed early); ZK_ERR_LIMIT when cap (in bytes) is too small, *n still set. */
 int zk_plonk_last_challenges(void* out, size_t cap, size_t* n);
+/* ---- the multi-open argument: ProverSHPLONK or ProverGWC ([3P-MEM] halo2_proofs v2023_01_20 src/poly/kzg/multiopen/{shplonk,gwc}/prover.rs) --------------------- *
+ * plonk::create_proof is generic over it; here it is a setting of the context (one context = one proving thread) that holds for every later proof the context
+ * creates, through zk_plonk_create_proof / _multi and zk_plonk_prove / _multi / _phased alike (descriptors and key handles).  Default: SHPLONK.
+ * GWC (ProverGWC::create_proof, the argument behind snark-verifier-sdk's gen_proof_gwc / gen_evm_proof_gwc): squeeze v; group the queries by point in order of first
+ * appearance (points unsorted, queries not deduplicated, their order kept inside a group); per group i with point z_i: B = sum_j v^j poly_j, W_i =
+ * commit(kate_division(B, z_i)) with Blind::default() and no rng draw, write_point(W_i).  The proof ends with one point per distinct opening point instead of SHPLONK's
+ * two, every byte before them is the SHPLONK proof's; zk_plonk_last_challenges then ends with v alone (n_challenges + 6 values).  One batched combination, one batched
+ * division and one MSM batch serve all groups.  An identity W_i: ZK_ERR_ARG (phase "multi-open").  A sharded descriptor (shard_world > 1) with GWC set: ZK_ERR_ARG
+ * before anything is committed.  zk_plonk_multiopen_set with any other value: ZK_ERR_ARG, the setting unchanged. */
+#define ZK_MULTIOPEN_SHPLONK 0u
+#define ZK_MULTIOPEN_GWC     1u
+int zk_plonk_multiopen_set(zk_ctx* ctx, uint32_t scheme);
+int zk_plonk_multiopen_get(zk_ctx* ctx, uint32_t* scheme);
 /* wall milliseconds of the nine phases (instances, advice, lookups, grand products, random poly, h numerator, h commit, evaluations, SHPLONK) of the
  * calling thread's last zk_plonk_create_proof / zk_plonk_create_proof_multi (a phase of an m-circuit proof covers all m circuits) */
 int zk_plonk_last_phase_ms(double out[9]);

@@ -65,8 +65,15 @@ extern "C" {
     pub fn zk_plonk_prove_phased(ctx: *mut ZkCtx, pk: u64, n_circuits: u32, advice: *mut *const c_void, advice_on_device: c_int, instances: *const *const c_void,
                                  instance_lens: *const u32, next_phase: Option<ZkPhaseFn>, next_phase_user: *mut c_void, rng: ZkRngFn, rng_user: *mut c_void,
                                  proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> c_int;
-    /// what the calling thread's last proof squeezed, canonical little endian: user challenges, theta, beta, gamma, y, x, SHPLONK's y, v, u
+    /// what the calling thread's last proof squeezed, canonical little endian: user challenges, theta, beta, gamma, y, x, SHPLONK's y, v, u (GWC: v alone)
     pub fn zk_plonk_last_challenges(out: *mut c_void, cap: usize, n: *mut usize) -> c_int;
+    /// the multi-open argument of every later proof of the context: 0 = ProverSHPLONK (the default), 1 = ProverGWC; any other value: ZK_ERR_ARG, the setting unchanged
+    pub fn zk_plonk_multiopen_set(ctx: *mut ZkCtx, scheme: u32) -> c_int;
+    pub fn zk_plonk_multiopen_get(ctx: *mut ZkCtx, scheme: *mut u32) -> c_int;
+    /// ProverGWC's polynomial work for all opening points at once: `count` ragged combinations in one launch, `count` divisions in the three launches of one
+    pub fn zk_fr_lincomb_batch_dev(ctx: *mut ZkCtx, polys: *const *const c_void, scalars: *const c_void, offsets: *const u32, count: usize, n: usize,
+                                   outs: *const *mut c_void) -> c_int;
+    pub fn zk_kate_division_batch_dev(ctx: *mut ZkCtx, a_dev: *const *const c_void, count: usize, n: usize, points: *const c_void, q_dev: *const *mut c_void) -> c_int;
     /// halo2's fold across circuits: out <- out * y^E + numerator (coset = u32::MAX: the whole extended domain; part 0 whole, 1 high, 2 low)
     pub fn zk_quotient_run_acc_dev(ctx: *mut ZkCtx, prog: u64, args: *const ZkQuotientArgs, coset: u32, part: u32) -> c_int;
 }

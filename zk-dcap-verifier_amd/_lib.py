@@ -517,6 +517,36 @@ class Backend:
         self._ck(self.lib.zk_fr_lincomb_dev(self.ctx, self._ptr_array(polys), sc.ctypes.data_as(C.c_void_p), C.c_size_t(len(polys)), C.c_size_t(n),
                                             C.c_void_p(_dptr(out_dev))))
 
+    def fr_lincomb_batch_dev(self, poly_lists, scalar_lists, n: int, outs):
+        """outs[p][i] = sum_j scalar_lists[p][j] * poly_lists[p][j][i] for every list p in ONE launch (GWC: one combination per opening point); the lists are ragged and
+        a polynomial may stand in several; scalar_lists[p]: (len, 4) Montgomery limbs.  No output may be an input or another output."""
+        polys = [q for lst in poly_lists for q in lst]
+        offsets = np.zeros(len(poly_lists) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum([len(lst) for lst in poly_lists])
+        sc = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.uint64).reshape(-1, 4) for s in scalar_lists]) if len(scalar_lists) else np.zeros((0, 4), dtype=np.uint64))
+        assert sc.shape[0] == len(polys) and len(outs) == len(poly_lists)
+        self._ck(self.lib.zk_fr_lincomb_batch_dev(self.ctx, self._ptr_array(polys), sc.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                                  C.c_size_t(len(poly_lists)), C.c_size_t(n), self._ptr_array(outs)))
+
+    def kate_division_batch_dev(self, a_devs, n: int, points, q_devs):
+        """q_devs[c] = a_devs[c] / (X - points[c]) for every column in the three launches of one division (the same column may be divided by several points)"""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64).reshape(-1, 4))
+        assert pts.shape[0] == len(a_devs) == len(q_devs)
+        self._ck(self.lib.zk_kate_division_batch_dev(self.ctx, self._ptr_array(a_devs), C.c_size_t(len(a_devs)), C.c_size_t(n), pts.ctypes.data_as(C.c_void_p),
+                                                     self._ptr_array(q_devs)))
+
+    # -- the multi-open argument of this context's proofs ------------------------------------------
+    MULTIOPEN = {"shplonk": 0, "gwc": 1}
+
+    def multiopen_set(self, scheme) -> None:
+        """zk_plonk_multiopen_set: "shplonk" / "gwc" (or the header's number) for every later native proof of this context"""
+        self._ck(self.lib.zk_plonk_multiopen_set(self.ctx, C.c_uint32(self.MULTIOPEN.get(scheme, scheme))))
+
+    def multiopen_get(self) -> str:
+        v = C.c_uint32()
+        self._ck(self.lib.zk_plonk_multiopen_get(self.ctx, C.byref(v)))
+        return {n: s for s, n in self.MULTIOPEN.items()}[v.value]
+
     # -- MockProver ------------------------------------------------------------------------------
     def _mock_desc(self, keep, *, k: int, blinding_factors: int, n_fixed: int, n_advice: int, n_instance: int, perm_columns, evaluator_blob: bytes,
                    lookup_input_blobs, lookup_table_blobs, fixed, advice=None, instances=None, perm_map_column=None, perm_map_row=None,

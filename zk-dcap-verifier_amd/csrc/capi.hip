@@ -28,6 +28,8 @@ int lookup_product_batch(zk_ctx* ctx, const void* const* cols4, size_t count, ui
 int eval_polynomial_batch(zk_ctx* ctx, const void* const* polys, size_t count, size_t n, const void* points, void* out);
 int kate_division(zk_ctx* ctx, const void* d_a, size_t n, const void* b_host, void* d_q);
 int fr_lincomb(zk_ctx* ctx, const void* const* polys, const void* scalars, size_t count, size_t n, void* d_out);
+int kate_division_batch(zk_ctx* ctx, const void* const* d_as, size_t count, size_t n, const void* points_host, void* const* d_qs);
+int fr_lincomb_batch(zk_ctx* ctx, const void* const* polys, const void* scalars, const uint32_t* offsets, size_t count, size_t n, void* const* outs);
 int pk_load(zk_ctx* ctx, uint64_t prog, const void* const* fixed, const void* const* sigma, const void* l0, const void* l_last, const void* l_active,
             int form, uint64_t* handle);
 int pk_release(zk_ctx* ctx, uint64_t h);
@@ -523,6 +525,21 @@ int zk_eval_polynomial_batch_dev(zk_ctx* ctx, const void* const* polys, size_t c
 } ZK_ABI_CATCH(ctx)
 int zk_kate_division_dev(zk_ctx* ctx, const void* a_dev, size_t n, const void* b, void* q_dev) ZK_ABI_TRY { ENTER; return kate_division(ctx, a_dev, n, b, q_dev); } ZK_ABI_CATCH(ctx)
 int zk_fr_lincomb_dev(zk_ctx* ctx, const void* const* polys_dev, const void* scalars, size_t count, size_t n, void* out_dev) ZK_ABI_TRY { ENTER; return fr_lincomb(ctx, polys_dev, scalars, count, n, out_dev); } ZK_ABI_CATCH(ctx)
+int zk_kate_division_batch_dev(zk_ctx* ctx, const void* const* a_dev, size_t count, size_t n, const void* points, void* const* q_dev) ZK_ABI_TRY { ENTER; return kate_division_batch(ctx, a_dev, count, n, points, q_dev); } ZK_ABI_CATCH(ctx)
+int zk_fr_lincomb_batch_dev(zk_ctx* ctx, const void* const* polys, const void* scalars, const uint32_t* offsets, size_t count, size_t n, void* const* outs) ZK_ABI_TRY { ENTER; return fr_lincomb_batch(ctx, polys, scalars, offsets, count, n, outs); } ZK_ABI_CATCH(ctx)
+// which multi-open argument the proofs of this context end with (prover.hip reads it once per proof, before anything is committed)
+int zk_plonk_multiopen_set(zk_ctx* ctx, uint32_t scheme) ZK_ABI_TRY {
+    NEED_CTX; LOCK;
+    if (scheme != ZK_MULTIOPEN_SHPLONK && scheme != ZK_MULTIOPEN_GWC) return ctx->fail(ZK_ERR_ARG, "zk_plonk_multiopen_set: scheme %u (0 = SHPLONK, 1 = GWC)", scheme);
+    ctx->multiopen = scheme;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
+int zk_plonk_multiopen_get(zk_ctx* ctx, uint32_t* scheme) ZK_ABI_TRY {
+    NEED_CTX; LOCK;
+    if (!scheme) return ctx->fail(ZK_ERR_ARG, "zk_plonk_multiopen_get: null argument");
+    *scheme = ctx->multiopen;
+    return ZK_OK;
+} ZK_ABI_CATCH(ctx)
 
 // ---- quotient -----------------------------------------------------------------------------------
 int zk_quotient_program_load(zk_ctx* ctx, const void* blob, size_t len, uint64_t* prog) ZK_ABI_TRY { ENTER; return quotient_program_load(ctx, blob, len, prog); } ZK_ABI_CATCH(ctx)

@@ -136,6 +136,7 @@ struct zk_ctx {
     char err[640] = {0};      // zk_last_error: a fixed buffer, so that reporting a failure (an exhausted heap included) allocates nothing
     hipStream_t stream = nullptr;
     zk::Tune tune;
+    uint32_t multiopen = ZK_MULTIOPEN_SHPLONK;   // zk_plonk_multiopen_set: the multi-open argument of every later proof of this context
     uint64_t next_handle = 1;
     std::map<uint64_t, zk::BaseTable> bases;
     std::list<zk::TwiddleSet> twiddles;    // (a list: a set's address survives the eviction of another)

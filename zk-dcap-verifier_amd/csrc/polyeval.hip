@@ -7,6 +7,7 @@
 // thread walks the polynomial in x^T) + an LDS tree sum, and kate_division is a 3-phase scan of the linear
 // recurrence q[i-1] = a[i] + b*q[i] carried as (value, multiplier) pairs.
 #include "ctx.h"
+#include <algorithm>
 #include <vector>
 
 namespace zk {
@@ -103,7 +104,7 @@ __device__ __forceinline__ u256 kd_lds_get(const uint4* lo, const uint4* hi, uin
     return o;
 }
 // mode 0: write the workgroup's (total, b^span) pair;  mode 1: carries[blk] holds the carry-in, write q.
-ZK_KERNEL void kd_scan_kernel(const void* a, uint32_t n, u256 b, int mode, void* carries, void* q) {
+__device__ __forceinline__ void kd_scan_body(const void* a, uint32_t n, const u256& b, int mode, void* carries, void* q) {
     __shared__ uint4 vlo[PE_T], vhi[PE_T], mlo[PE_T], mhi[PE_T];
     const uint32_t tid = threadIdx.x, T = blockDim.x;
     const uint32_t span = T * KD_E, t0 = blockIdx.x * span + tid * KD_E;
@@ -150,9 +151,16 @@ ZK_KERNEL void kd_scan_kernel(const void* a, uint32_t n, u256 b, int mode, void*
         bp = Fr::mul(bp, b);
     }
 }
+ZK_KERNEL void kd_scan_kernel(const void* a, uint32_t n, u256 b, int mode, void* carries, void* q) { kd_scan_body(a, n, b, mode, carries, q); }
+// `count` divisions in one launch, the column in blockIdx.y: column c divides as[c] by (X - points[c]) into qs[c]; its workgroups' pairs (mode 0: 2 per workgroup) or
+// carry-ins (mode 1: 1 per workgroup) lie back to back per column.  (The single call keeps its own entry: its divisor and pointers are kernel arguments, so it uploads nothing.)
+ZK_KERNEL void kd_scan_batch_kernel(const void* const* as, uint32_t n, const void* points, int mode, void* carries, void* const* qs) {
+    const uint32_t c = blockIdx.y;
+    kd_scan_body(as[c], n, load_u256(points, c), mode, (char*)carries + (size_t)c * gridDim.x * (mode == 0 ? 64 : 32), qs[c]);
+}
 // single workgroup: carries[2*blk] = (total, mult) pairs -> out[blk] = carry-in of workgroup blk: the same (value, multiplier) scan as
 // inside kd_scan_kernel, one pair per thread per round of PE_T workgroups (a serial walk over a few hundred dependent products cost 0.2 ms)
-ZK_KERNEL void kd_carry_kernel(void* carries, uint32_t nblk, void* out) {
+__device__ __forceinline__ void kd_carry_body(void* carries, uint32_t nblk, void* out) {
     __shared__ uint4 vlo[PE_T], vhi[PE_T], mlo[PE_T], mhi[PE_T];
     const uint32_t tid = threadIdx.x, T = blockDim.x;
     u256 cin = Fr::zero();                                  // carry into the current round of T workgroups
@@ -183,12 +191,21 @@ ZK_KERNEL void kd_carry_kernel(void* carries, uint32_t nblk, void* out) {
         __syncthreads();
     }
 }
+ZK_KERNEL void kd_carry_kernel(void* carries, uint32_t nblk, void* out) { kd_carry_body(carries, nblk, out); }
+// one workgroup per column (blockIdx.x) of a batched division
+ZK_KERNEL void kd_carry_batch_kernel(void* carries, uint32_t nblk, void* out) {
+    kd_carry_body((char*)carries + (size_t)blockIdx.x * nblk * 64, nblk, (char*)out + (size_t)blockIdx.x * nblk * 32);
+}
 
 // ---- linear combinations (SHPLONK / multiopen polynomial combos) -----------------------------------
 // out[i] = sum_j s_j * p_j[i]: the `poly * power_of_y` ... `reduce(|acc, poly| acc + &poly)` chains of
 // halo2_proofs src/poly/kzg/multiopen/shplonk/prover.rs, one pass over all inputs instead of one pass per term.
-// args: [count pointers | pad to 32 B | count scalars]
-ZK_KERNEL void pe_lincomb_kernel(const void* const* polys, const void* scalars32, uint32_t count, size_t n, void* out) {
+// Several combinations in one launch (GWC / multiopen: one per opening point), the combination in blockIdx.y: combination p sums the terms offsets[p] .. offsets[p+1]
+// of the two lists into outs[p]; a single combination is the launch with gridDim.y = 1.
+// args: [total pointers | pad to 32 B | total scalars | combinations + 1 offsets | pad to 8 B | combinations out pointers]
+ZK_KERNEL void pe_lincomb_kernel(const void* const* polys, const void* scalars32, const uint32_t* offsets, size_t n, void* const* outs) {
+    const uint32_t first = offsets[blockIdx.y], last = offsets[blockIdx.y + 1];      // this combination's terms: first <= j < last
+    void* out = outs[blockIdx.y];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     // terms are taken SIX at a time on carry-free limbs with ONE Montgomery reduction for the six products (field29.cuh, sums of products: 96 multiplications per term against
@@ -197,10 +214,10 @@ ZK_KERNEL void pe_lincomb_kernel(const void* const* polys, const void* scalars32
     for (; i < n; i += stride) {
         u261 total = Fr29::zero();
         uint32_t chunks = 0;
-        for (uint32_t j0 = 0; j0 < count; j0 += 6) {
+        for (uint32_t j0 = first; j0 < last; j0 += 6) {
             Fr29::Dot29 d;
             Fr29::dot_clear(d);
-            const uint32_t j1 = j0 + 6 < count ? j0 + 6 : count;
+            const uint32_t j1 = j0 + 6 < last ? j0 + 6 : last;
             for (uint32_t j = j0; j < j1; j++) Fr29::dot_add(d, Fr29::from32<0>(load_u256(polys[j], i)), Fr29::from32<0>(load_u256(scalars32, j)));
             total = Fr29::carry(Fr29::add(total, Fr29::dot_reduce(d)));              // every chunk adds less than 1.3 p
             if ((++chunks & 15u) == 0) total = Fr29::reduce_small(total);            // (below 32 p at all times)
@@ -251,30 +268,105 @@ int kate_division(zk_ctx* ctx, const void* d_a, size_t n, const void* b_host, vo
     return ZK_OK;
 }
 
+// `count` combinations over `total` terms (validated by the callers): the argument block travels in one copy, the kernel runs once
+static int lincomb_launch(zk_ctx* ctx, const void* const* polys, const void* scalars, const uint32_t* offsets, size_t count, size_t n, void* const* outs) {
+    const size_t total = offsets[count];
+    const size_t off_sc = (total * sizeof(void*) + 31) & ~(size_t)31, off_of = off_sc + total * 32, off_out = (off_of + (count + 1) * 4 + 7) & ~(size_t)7,
+                 bytes = off_out + count * sizeof(void*);
+    std::vector<uint64_t> args((bytes + 7) / 8, 0);
+    char* h = (char*)args.data();
+    memcpy(h, polys, total * sizeof(void*));
+    {
+        u256 c32 = Fr::zero();                                       // the kernel multiplies on 29-bit limbs (Montgomery radix 2^261): scalars as x 2^261 operands
+        c32.v[0] = 32;
+        c32 = Fr::to_mont(c32);
+        for (size_t j = 0; j < total; j++) { u256 v; memcpy(&v, (const char*)scalars + 32 * j, 32); v = Fr::mul(v, c32); memcpy(h + off_sc + 32 * j, &v, 32); }
+    }
+    memcpy(h + off_of, offsets, (count + 1) * 4);
+    memcpy(h + off_out, outs, count * sizeof(void*));
+    ZK_HIP(ctx->ws_tmp.ensure(bytes));
+    char* base = (char*)ctx->ws_tmp.p;
+    hipStream_t st = ctx->stream;
+    ZK_HIP(hipMemcpyAsync(base, h, bytes, hipMemcpyHostToDevice, st));
+    const int blk = ctx->tune.vec_block;
+    size_t grid = (n + blk - 1) / blk; if (grid > 8192) grid = 8192;
+    ZK_LAUNCH(pe_lincomb_kernel, dim3((uint32_t)grid, (uint32_t)count), blk, 0, st, (const void* const*)base, (const void*)(base + off_sc), (const uint32_t*)(base + off_of), n,
+              (void* const*)(base + off_out));
+    ZK_CHECK_LAUNCH();
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
+// `count` divisions, each by its own point, in the three launches of one: the column is a grid dimension, the carry pairs and carry-ins lie per column in ws_tmp
+// [count x nblk pairs | count x nblk carry-ins | count points | count column pointers a | count column pointers q].  The same column may be divided by several points; a
+// quotient buffer that is also an input or another quotient is refused (the second scan reads a while other workgroups write q).
+int kate_division_batch(zk_ctx* ctx, const void* const* d_as, size_t count, size_t n, const void* points_host, void* const* d_qs) {
+    if (!d_as || !points_host || !d_qs) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: null argument");
+    if (count == 0 || count > 65535) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: count out of range");
+    if (n < 2 || n > (1u << 27)) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: n = %zu out of range", n);
+    for (size_t c = 0; c < count; c++) {
+        if (!d_as[c] || !d_qs[c]) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: null column %zu", c);
+        for (size_t d = 0; d < c; d++) if (d_qs[d] == d_qs[c]) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: quotients %zu and %zu are the same buffer", d, c);
+        for (size_t d = 0; d < count; d++) if (d_as[d] == d_qs[c]) return ctx->fail(ZK_ERR_ARG, "zk_kate_division_batch_dev: quotient %zu is also input %zu", c, d);
+    }
+    const uint32_t span = PE_T * KD_E, nblk = (uint32_t)((n + span - 1) / span);
+    const size_t off_cin = count * (size_t)nblk * 64, off_pt = off_cin + count * (size_t)nblk * 32, off_a = off_pt + count * 32, off_q = off_a + count * sizeof(void*),
+                 arg_bytes = count * 32 + 2 * count * sizeof(void*);
+    std::vector<uint64_t> args(arg_bytes / 8);
+    char* h = (char*)args.data();
+    memcpy(h, points_host, count * 32);
+    memcpy(h + (off_a - off_pt), d_as, count * sizeof(void*));
+    memcpy(h + (off_q - off_pt), d_qs, count * sizeof(void*));
+    ZK_HIP(ctx->ws_tmp.ensure(off_pt + arg_bytes));
+    char* base = (char*)ctx->ws_tmp.p;
+    hipStream_t st = ctx->stream;
+    ZK_HIP(hipMemcpyAsync(base + off_pt, h, arg_bytes, hipMemcpyHostToDevice, st));
+    const void* const* as = (const void* const*)(base + off_a);
+    void* const* qs = (void* const*)(base + off_q);
+    const dim3 grid(nblk, (uint32_t)count);
+    ZK_LAUNCH(kd_scan_batch_kernel, grid, PE_T, 0, st, as, (uint32_t)n, (const void*)(base + off_pt), 0, (void*)base, qs);
+    ZK_CHECK_LAUNCH();
+    ZK_LAUNCH(kd_carry_batch_kernel, (uint32_t)count, PE_T, 0, st, (void*)base, nblk, (void*)(base + off_cin));
+    ZK_CHECK_LAUNCH();
+    ZK_LAUNCH(kd_scan_batch_kernel, grid, PE_T, 0, st, as, (uint32_t)n, (const void*)(base + off_pt), 1, (void*)(base + off_cin), qs);
+    ZK_CHECK_LAUNCH();
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
 int fr_lincomb(zk_ctx* ctx, const void* const* polys, const void* scalars, size_t count, size_t n, void* d_out) {
     if (!polys || !scalars || !d_out) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_dev: null argument");
     if (count == 0 || count > 65535) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_dev: count out of range");
     if (n == 0) return ZK_OK;
     for (size_t i = 0; i < count; i++) if (!polys[i]) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_dev: null polynomial %zu", i);
-    const size_t off_sc = (count * sizeof(void*) + 31) & ~(size_t)31;
-    ZK_HIP(ctx->ws_tmp.ensure(off_sc + count * 32));
-    char* base = (char*)ctx->ws_tmp.p;
-    hipStream_t st = ctx->stream;
-    ZK_HIP(hipMemcpyAsync(base, polys, count * sizeof(void*), hipMemcpyHostToDevice, st));
-    std::vector<u256> sc32(count);                                   // the kernel multiplies on 29-bit limbs (Montgomery radix 2^261): scalars as x 2^261 operands
-    {
-        u256 c32 = Fr::zero();
-        c32.v[0] = 32;
-        c32 = Fr::to_mont(c32);
-        for (size_t j = 0; j < count; j++) { u256 v; memcpy(&v, (const char*)scalars + 32 * j, 32); sc32[j] = Fr::mul(v, c32); }
+    const uint32_t offsets[2] = {0, (uint32_t)count};
+    return lincomb_launch(ctx, polys, scalars, offsets, 1, n, &d_out);
+}
+
+// ragged lists: combination p is over polys[offsets[p] .. offsets[p+1]) with the matching scalars (a polynomial may stand in several lists).  Unlike the single call no
+// output may be an input: another combination of the same launch may still be reading it.
+int fr_lincomb_batch(zk_ctx* ctx, const void* const* polys, const void* scalars, const uint32_t* offsets, size_t count, size_t n, void* const* outs) {
+    if (!polys || !scalars || !offsets || !outs) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: null argument");
+    if (count == 0 || count > 65535) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: count out of range");
+    if (offsets[0] != 0) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: offsets[0] = %u, expected 0", offsets[0]);
+    for (size_t p = 0; p < count; p++) {
+        if (offsets[p + 1] <= offsets[p]) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: combination %zu is empty (offsets %u, %u)", p, offsets[p], offsets[p + 1]);
+        if (offsets[p + 1] - offsets[p] > 65535) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: combination %zu has more than 65535 terms", p);
     }
-    ZK_HIP(hipMemcpyAsync(base + off_sc, sc32.data(), count * 32, hipMemcpyHostToDevice, st));
-    const int blk = ctx->tune.vec_block;
-    size_t grid = (n + blk - 1) / blk; if (grid > 8192) grid = 8192;
-    ZK_LAUNCH(pe_lincomb_kernel, (uint32_t)grid, blk, 0, st, (const void* const*)base, (const void*)(base + off_sc), (uint32_t)count, n, d_out);
-    ZK_CHECK_LAUNCH();
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    const size_t total = offsets[count];
+    if (total > (1u << 22)) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: %zu terms in all, at most 2^22", total);
+    for (size_t i = 0; i < total; i++) if (!polys[i]) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: null polynomial %zu", i);
+    std::vector<const void*> seen(polys, polys + total);
+    std::sort(seen.begin(), seen.end());
+    std::vector<const void*> out_sorted(outs, outs + count);
+    std::sort(out_sorted.begin(), out_sorted.end());
+    for (size_t p = 0; p < count; p++) {
+        if (!outs[p]) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: null output %zu", p);
+        if (std::binary_search(seen.begin(), seen.end(), (const void*)outs[p])) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: output %zu is also an input", p);
+        if (p && out_sorted[p] == out_sorted[p - 1]) return ctx->fail(ZK_ERR_ARG, "zk_fr_lincomb_batch_dev: two outputs are the same buffer");
+    }
+    if (n == 0) return ZK_OK;
+    return lincomb_launch(ctx, polys, scalars, offsets, count, n, outs);
 }
 
 }  // namespace zk

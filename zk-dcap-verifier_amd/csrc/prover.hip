@@ -331,6 +331,43 @@ int shplonk_create_proof(zk_ctx* ctx, Arena& mem, Transcript& tr, const std::vec
     return commit(tmp1);
 }
 
+// ProverGWC::create_proof(transcript, queries) — plonk/gwc.py's function of the same name ([3P-MEM] halo2_proofs v2023_01_20 src/poly/kzg/multiopen/gwc/prover.rs): the
+// same `queries`; squeeze v, group them by point in order of first appearance (a linear scan: points unsorted, queries not deduplicated, their order kept), and per
+// group commit W = kate_division(sum_j v^j poly_j, point) — the constant term, hence the "- eval" of halo2's poly_batch, never enters the quotient.  All groups at
+// once: one batched combination, one batched division, and `commit` takes the P witness columns as one batch and writes their points in group order.
+int gwc_create_proof(zk_ctx* ctx, Arena& mem, Transcript& tr, const std::vector<Query>& queries, size_t n, const std::function<int(const std::vector<void*>&)>& commit) {
+    const size_t col_bytes = n * 32;
+    const Fe v = squeeze_noted(tr);
+    struct Group { u256 key; Fe point; std::vector<size_t> members; };            // key: the canonical point
+    std::vector<Group> groups;
+    for (size_t i = 0; i < queries.size(); i++) {
+        const u256 cp = Fr::from_mont(queries[i].point);
+        size_t gi = 0;
+        while (gi < groups.size() && !Fr::eq(groups[gi].key, cp)) gi++;
+        if (gi == groups.size()) groups.push_back(Group{cp, queries[i].point, {}});
+        groups[gi].members.push_back(i);
+    }
+    const size_t P = groups.size();
+    if (!P) return ZK_OK;
+    std::vector<const void*> polys;
+    std::vector<Fe> scal, pts;
+    std::vector<uint32_t> offsets{0};
+    for (const Group& g : groups) {
+        Fe vp = Fr::one();                                                        // the j-th query of a group gets v^j, from v^0 in every group
+        for (size_t qi : g.members) { polys.push_back(queries[qi].poly); scal.push_back(vp); vp = Fr::mul(vp, v); }
+        offsets.push_back((uint32_t)polys.size());
+        pts.push_back(g.point);
+    }
+    std::vector<void*> batch(P, nullptr), wit(P, nullptr);
+    PK(mem.take(batch, col_bytes));
+    PK(mem.take(wit, col_bytes));
+    PK(zk_fr_lincomb_batch_dev(ctx, polys.data(), packed(scal).data(), offsets.data(), P, n, batch.data()));
+    PK(zk_kate_division_batch_dev(ctx, (const void* const*)batch.data(), P, n, packed(pts).data(), wit.data()));
+    for (void* b : batch) mem.give_back(b);
+    for (void* w : wit) PK(zk_dev_zero(ctx, (char*)w + (n - 1) * 32, 32));         // n - 1 coefficients: the column the commitment reads has n
+    return commit(wit);
+}
+
 thread_local double g_phase_ms[9];                                    // wall time of the phases of the calling thread's last proof (zk_plonk_last_phase_ms)
 struct PhaseClock {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -376,6 +413,7 @@ struct Proof {
     uint32_t k = 0, ek = 0, bf = 0, L = 0, A = 0, I = 0, chunk = 0, n_sets = 0, n_pieces = 0, world = 1, rank = 0, n_phases = 1, n_chal = 0;
     size_t n = 0, en = 0, col_bytes = 0, usable = 0, n_loc = 0, shard_lo = 0, mA = 0, mI = 0, mL = 0, mS = 0, W = 0;
     bool sharded = false, by_cosets = false, side = false;
+    uint32_t multiopen = ZK_MULTIOPEN_SHPLONK;                         // the context's setting when the proof began (zk_plonk_multiopen_set)
     QuotUnits qu;                                                      // the quotient's units of this rank (sharded)
     // Destruction runs upwards from here and the order matters: `draws` joins the rng thread first, then `lane` joins the helper thread, and only then `mem` returns
     // the buffers those threads write to the pool.  The exchange arena (ShardSignal::xmem, the entry's) outlives all of it.
@@ -425,6 +463,9 @@ struct Proof {
         world = pk->shard_world > 1 ? pk->shard_world : 1; rank = world > 1 ? pk->shard_rank : 0;
         sharded = world > 1;
         if (sharded && m > 1) return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof_multi: %u circuits on a sharded key (shard_world %u): one proof over several circuits runs on one GPU", m, world);
+        PK(zk_plonk_multiopen_get(ctx, &multiopen));
+        if (sharded && multiopen == ZK_MULTIOPEN_GWC)
+            return pk_fail(ctx, ZK_ERR_ARG, "zk_plonk_create_proof: the GWC multi-open on a sharded key (shard_world %u): one proof over several GPUs ends with SHPLONK", world);
         A = pk->n_advice; I = pk->n_instance;                         // per circuit; circuit c's columns are [c * A, (c + 1) * A) etc. (circuit-major)
         if ((pk->n_fixed && (!pk->fixed_values || !pk->fixed_polys)) || (pk->n_perm_columns && (!pk->perm_columns || !pk->sigma_values || !pk->sigma_polys)) ||
             (L && (!pk->lookup_input_programs || !pk->lookup_table_programs || !pk->lookup_table_key)) || (pk->n_advice_queries && !pk->advice_queries) ||
@@ -883,9 +924,10 @@ struct Proof {
         for (size_t i = 0; i + 1 < q.size(); i++) tr.write_scalar(q[i].eval);            // h's evaluation is the verifier's to derive
         return ZK_OK;
     }
-    // ---- 9. ProverSHPLONK: queries in the multi-open order ---------------------------------------------------------------------------------------------------------------
+    // ---- 9. ProverSHPLONK or ProverGWC (the context's setting): queries in the multi-open order --------------------------------------------------------------------------
     int multi_open() {
         std::stable_sort(q.begin(), q.end(), [](const Query& a, const Query& b) { return a.open < b.open; });
+        if (multiopen == ZK_MULTIOPEN_GWC) return gwc_create_proof(ctx, mem, tr, q, n, [this](const std::vector<void*>& polys) { return commit(pk->srs_g, polys); });
         return shplonk_create_proof(ctx, mem, tr, q, n, [this](void* poly) { return commit(pk->srs_g, {poly}); });
     }
     // A commitment to the zero polynomial is the identity, which no transcript can absorb (Transcript::bad_point; halo2's common_point: "cannot write points at infinity

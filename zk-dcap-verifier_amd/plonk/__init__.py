@@ -22,3 +22,4 @@ from .keygen import KeyView, NativeKey, NativeKeygen, ProvingKey, VerifyingKey, 
 from .prover import create_proof  # noqa: F401
 from .native import NativeProver, PhasedProver, create_proof_native, last_challenges  # noqa: F401
 from .shplonk import ProverSHPLONK  # noqa: F401
+from .gwc import ProverGWC  # noqa: F401

@@ -7,6 +7,7 @@ buffers and program handles) into the `zk_plonk_pk_desc` the C entry point takes
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Sequence
 
@@ -18,6 +19,25 @@ from ..kzg import ParamsKZG
 from .keygen import ProvingKey
 
 RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_void_p)
+
+
+@contextlib.contextmanager
+def _multiopen(be, scheme):
+    """the context's multi-open setting (zk_plonk_multiopen_set) for the duration of one proof; None leaves the context as the caller set it"""
+    if scheme is None:
+        yield
+        return
+    before = be.multiopen_get()
+    be.multiopen_set(scheme)
+    try:
+        yield
+    finally:
+        be.multiopen_set(before)
+
+
+def _opening_points(cs) -> int:
+    """an upper bound of the distinct opening points of a proof (GWC writes one commitment per point): the rotations queried, and x, x_next, x_prev, x_last"""
+    return len({r for _, r in cs.advice_queries()} | {r for _, r in cs.fixed_queries()} | {0, 1, -1, -(cs.blinding_factors() + 1)})
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 
 
@@ -103,8 +123,10 @@ class PhasedProver:
     challenges, circuit)` is the caller's synthesis of a later phase: it receives the canonical challenge values known so far (0 where not yet squeezed) and returns
     {column: values} for every column of that phase of that circuit — (n, 4) uint64 Montgomery host arrays, or device buffers when the phase-0 columns are."""
 
-    def __init__(self, params: ParamsKZG, pk: ProvingKey, key=None):
+    def __init__(self, params: ParamsKZG, pk: ProvingKey, key=None, multiopen: str | None = None):
+        """multiopen: "shplonk" / "gwc" for this prover's proofs, or None: whatever the context is set to (Backend.multiopen_set; SHPLONK unless changed)"""
         from .keygen import NativeKey
+        self.multiopen = multiopen
         self.params, self.pk, self.be = params, pk, pk.backend
         self.key = key if key is not None else NativeKey(params, pk)
         self.be = self.key.backend
@@ -112,7 +134,7 @@ class PhasedProver:
         cs = pk.vk.cs
         self.phase_of = cs._advice_phases()
         self.per_circuit = 32 * (cs.num_advice_columns + 3 * len(cs.lookups) + len(cs.permutation_columns) + len(cs.advice_queries()) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups))
-        self.shared = 32 * (16 + len(cs.fixed_queries()) + 1 + len(cs.permutation_columns) + 8)
+        self.shared = 32 * (16 + len(cs.fixed_queries()) + 1 + len(cs.permutation_columns) + 8 + _opening_points(cs))
 
     def release(self):
         if self._own_key:
@@ -172,8 +194,9 @@ class PhasedProver:
         cap = self.shared + m * self.per_circuit
         out = np.empty(cap, dtype=np.uint8)
         ln = C.c_size_t()
-        rc = be.lib.zk_plonk_prove_phased(be.ctx, C.c_uint64(self.key.handle), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, phase_cb, None, cb, None,
-                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
+        with _multiopen(be, self.multiopen):
+            rc = be.lib.zk_plonk_prove_phased(be.ctx, C.c_uint64(self.key.handle), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, phase_cb, None, cb, None,
+                                              out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
         if errors:
             raise errors[0]
         be._ck(rc)
@@ -185,12 +208,14 @@ class NativeProver:
 
     TRANSCRIPTS = {"blake2b": 0, "poseidon": 1, "evm": 2}
 
-    def __init__(self, params: ParamsKZG, pk: ProvingKey, transcript: str = "blake2b", exchange=None):
-        """exchange (sharded params only): the ranks' collective — an object with `all_gather(send_ptr, recv_ptr, nbytes)` and, optionally, the device
+    def __init__(self, params: ParamsKZG, pk: ProvingKey, transcript: str = "blake2b", exchange=None, multiopen: str | None = None):
+        """multiopen: "shplonk" / "gwc" for this prover's proofs, or None: whatever the context is set to (Backend.multiopen_set; SHPLONK unless changed).
+        exchange (sharded params only): the ranks' collective — an object with `all_gather(send_ptr, recv_ptr, nbytes)` and, optionally, the device
         buffers `send` / `recv` / `cap` the library should exchange through (TorchExchange above); every rank must prove with the same witness and rng stream."""
         assert (params.world == 1) == (pk.coset_parts is None or pk.pieces_from_cosets), "a sharded SRS goes with a proving key built on it (keygen(params.sharded(..)))"
         assert params.world == 1 or exchange is not None, "a sharded proof needs the ranks' all-gather"
         self.params, self.pk, self.be = params, pk, pk.backend
+        self.multiopen = multiopen
         cs = pk.vk.cs
         self._keep = []
 
@@ -265,7 +290,7 @@ class NativeProver:
         d.draw_schedule = 1                                 # halo2_proofs v2023_01_20's order of Fr::random draws (prover.py draw_plan): the only schedule the library knows
         self.desc = d
         self.proof_cap = (64 if transcript == "evm" else 32) * (cs.num_advice_columns + 3 * len(cs.lookups) + len(cs.permutation_columns) + 16 +
-                               len(aq) + len(fq) + 1 + len(cs.permutation_columns) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups) + 8)
+                               len(aq) + len(fq) + 1 + len(cs.permutation_columns) + 3 * len(cs.permutation_columns) + 5 * len(cs.lookups) + 8 + _opening_points(cs))
 
     def proof_cap_for(self, n_circuits: int) -> int:
         """an upper bound of the proof bytes of one proof over n_circuits circuits (the per-circuit commitments and evaluations n_circuits times)"""
@@ -308,12 +333,13 @@ class NativeProver:
         cb = RNG_FN(draw)
         out = np.empty(max(cap, 1), dtype=np.uint8)
         ln = C.c_size_t()
-        if m == 0:
-            rc = be.lib.zk_plonk_create_proof(be.ctx, C.byref(d), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
-                                              out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
-        else:
-            rc = be.lib.zk_plonk_create_proof_multi(be.ctx, C.byref(d), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
-                                                    out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
+        with _multiopen(be, self.multiopen):
+            if m == 0:
+                rc = be.lib.zk_plonk_create_proof(be.ctx, C.byref(d), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
+                                                  out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
+            else:
+                rc = be.lib.zk_plonk_create_proof_multi(be.ctx, C.byref(d), C.c_uint32(m), adv, C.c_int(1 if on_device else 0), inst_ptrs, lens, cb, None,
+                                                        out.ctypes.data_as(C.c_void_p), C.c_size_t(cap), C.byref(ln))
         if errors:
             raise errors[0]
         if getattr(self, "comm_errors", None):

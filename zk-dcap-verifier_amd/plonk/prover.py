@@ -32,6 +32,7 @@ from ..kzg import ParamsKZG
 from ..permutation import lookup_commit_products, permutation_commit, permute_expression_pairs
 from .circuit import ADVICE, FIXED, INSTANCE
 from .keygen import ProvingKey
+from .gwc import ProverGWC, group_by_point
 from .shplonk import ProverQuery, ProverSHPLONK
 
 
@@ -73,7 +74,7 @@ class _Joiner:
 
 
 def create_proof(params: ParamsKZG, pk: ProvingKey, advice: Sequence, instances: Sequence[Sequence[int]], rng: np.random.Generator, transcript,
-                 timings: Optional[dict] = None, capture: Optional[dict] = None, phase_io=None, next_phase=None) -> dict:
+                 timings: Optional[dict] = None, capture: Optional[dict] = None, phase_io=None, next_phase=None, multiopen: str = "shplonk") -> dict:
     """advice: cs.num_advice_columns columns of n rows — (n, 4) uint64 Montgomery host arrays or device buffers; rows past
     `usable_rows` are overwritten with blinding and device buffers are consumed (they hold coefficients afterwards).  instances:
     canonical ints per instance column.  Writes the proof into `transcript` and returns bookkeeping for tests / benches
@@ -81,16 +82,18 @@ def create_proof(params: ParamsKZG, pk: ProvingKey, advice: Sequence, instances:
     along the way are released (back to the backend's pool) on success and on failure alike.  `capture` (measurement tooling only): receives host
     copies of the proof's committed Lagrange columns and challenges, so that a driver of the per-call host-buffer entry points can replay them.
     next_phase(phase, challenges) -> {column: values}: the caller's synthesis of advice phase 1, 2 from the canonical challenge values squeezed so far (0 where not yet
-    squeezed); the entries of later-phase columns in `advice` are ignored."""
+    squeezed); the entries of later-phase columns in `advice` are ignored.  multiopen: "shplonk" (ProverSHPLONK, shplonk.py) or "gwc" (ProverGWC, gwc.py) — the
+    multi-open argument the proof ends with; every byte before it is the same."""
+    assert multiopen in ("shplonk", "gwc"), multiopen
     owned: List = []
     try:
-        return _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture, phase_io, next_phase)
+        return _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture, phase_io, next_phase, multiopen)
     finally:
         for d in owned:
             d.free()
 
 
-def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture=None, phase_io=None, next_phase=None) -> dict:
+def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned, capture=None, phase_io=None, next_phase=None, multiopen="shplonk") -> dict:
     be, cs, k, n = pk.backend, pk.vk.cs, params.k, params.n
     dom = pk.domain
     ek, en = dom.extended_k, dom.extended_n
@@ -417,6 +420,11 @@ def _create_proof(params, pk, advice, instances, rng, transcript, timings, owned
     q_h = take()
     reads("9_shplonk", lag + [random_poly, h_poly])
     queries = q_adv + q_perm_a + list(reversed(q_perm_last)) + q_lk + q_fix + q_sigma + [q_h, q_rand]
-    ProverSHPLONK(params).create_proof(transcript, queries)
+    n_open = 2
+    if multiopen == "gwc":
+        ProverGWC(params).create_proof(transcript, queries)
+        n_open = len(group_by_point(queries))
+    else:
+        ProverSHPLONK(params).create_proof(transcript, queries)
     lap("9_shplonk")
-    return {"commitments": nA + 2 * L + nZ + L + 1 + n_pieces + 2, "evals": len(evals) - 1, "h_eval": evals[-1]}
+    return {"commitments": nA + 2 * L + nZ + L + 1 + n_pieces + n_open, "evals": len(evals) - 1, "h_eval": evals[-1]}
