@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY — an independent CPU prover: halo2's keygen_vk / keygen_pk / create_proof / ProverSHPLONK over Python integers.
+"""TEST INFRASTRUCTURE ONLY — an independent CPU prover: halo2's keygen_vk / keygen_pk / create_proof / ProverSHPLONK and ProverGWC over Python integers.
 
 Why it exists: the reference's prover IS a CPU `create_proof` (circuits/src/sgx_dcap_verifier.rs:799-823: gen_srs, keygen_vk, keygen_pk,
 create_proof with a Blake2b transcript; crates/p256-ecdsa/src/base.rs:193-212 for stack B) and its only pin on the prover is that
@@ -8,14 +8,16 @@ witness, same seeded RNG stream, same transcript => the GPU must emit THESE byte
 
 Restated from the published protocol of halo2_proofs 0.2.0 (zkwebauthn @ c254c75, Cargo.lock:1314-1327): src/plonk/{keygen,prover}.rs,
 src/plonk/{permutation,lookup,vanishing}/prover.rs, src/plonk/permutation/keygen.rs (Assembly), src/poly/domain.rs,
-src/poly/kzg/{commitment.rs, multiopen/shplonk/prover.rs} ([3P-MEM]: the pinned crate is not on this machine — SURVEY.md §3.1, App. C; parity
-with the Rust prover's bytes stays UNPINNED).  It shares no code with the product: polynomials are lists of canonical
+src/poly/kzg/{commitment.rs, multiopen/shplonk/prover.rs, multiopen/gwc.rs, multiopen/gwc/prover.rs} ([3P-MEM]: the pinned crate is not on this machine —
+SURVEY.md §3.1, App. C; parity with the Rust prover's bytes stays UNPINNED).  It shares no code with the product: polynomials are lists of canonical
 Python ints, NTTs are oracle/pyref.py's, the quotient is evaluated from its DEFINITION row by row (no GraphEvaluator, no ZKQ1 program),
 lookups are permuted with sorted() and a dict, grand products use pow(x, -1, r); only the multi-scalar multiplications go through the C
 oracle (oracle/bn254_oracle.c, halo2's best_multiexp restated).  The circuit description (`cs`: column counts, gate / lookup expression
 trees, equality columns, query lists) is read as DATA, the way oracle/verifier.py reads it.  Sized for k <= 10.
 create_proof_multi is the whole of it — one proof over m circuits, advice in phases, user challenges (the draw and transcript order
-is written out here a second time, nothing is taken from the product's draw plan); create_proof is its m = 1 call without a callback.
+is written out here a second time, nothing is taken from the product's draw plan); create_proof is its m = 1 call without a callback.  Both end with the
+multi-open argument the caller names: multiopen="shplonk" (the default; every committed SHPLONK golden) or "gwc" (_gwc_multiopen below, restated on its own: nothing
+of it comes from zk-dcap-verifier_amd/plonk/gwc.py or from tests/gwc_verifier.py).
 
 Spec points that are this repo's (mirror = oracle, neither checkable against Rust here): vk.transcript_repr (Blake2b of the key's Debug-like
 rendering), the rejection sampler standing in for Fr::random, the order of the random draws.
@@ -276,14 +278,53 @@ def _phase_lists(cs):
     return ap, list(getattr(cs, "challenge_phase", None) or [])
 
 
-def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.Generator, require_satisfied: bool = True) -> bytes:
+# ---- ProverGWC ([3P-MEM] halo2_proofs src/poly/kzg/multiopen/gwc.rs construct_intermediate_sets, gwc/prover.rs create_proof) -------------------------------------------
+def _gwc_groups(queries):
+    """gwc.rs: the queries (key, poly, point, eval) grouped by point.  The queries are walked in order; the groups made so far are scanned linearly for one whose point
+    has the same field value (points are canonical ints here, so == is that); the query is appended to it, or else opens a new group at the end.  Groups therefore stand in
+    order of first appearance: points are NOT sorted, queries are NOT merged (two queries that name the same polynomial at the same point stay two members) and keep
+    their order inside a group."""
+    groups = []                                                      # [[point, [query, ..]], ..]
+    for q in queries:
+        for g in groups:
+            if g[0] == q[2]:
+                g[1].append(q)
+                break
+        else:
+            groups.append([q[2], [q]])
+    return groups
+
+
+def _gwc_multiopen(tr: _Writer, params: Params, queries, n: int, opening_out: dict | None = None) -> list:
+    """gwc/prover.rs: v = squeeze; per group, in group order, with point z: B = sum_j v^j poly_j and e = sum_j v^j eval_j, j counting from 0 inside EVERY group;
+    W = commit(kate_division(B - e, z)); write_point(W).  Nothing is squeezed after v and no rng draw is made (the commitments carry Blind::default()).  Returns [v]."""
+    v = tr.squeeze()
+    groups = _gwc_groups(queries)
+    for z, members in groups:
+        B, e, vpow = [0] * n, 0, 1
+        for _, poly, _, ev in members:
+            for i, c_ in enumerate(poly):
+                B[i] = (B[i] + vpow * c_) % R
+            e = (e + vpow * ev) % R
+            vpow = vpow * v % R
+        B[0] = (B[0] - e) % R                                        # B - e: B(z) = e, so the division below is exact
+        assert _poly_eval(B, z) == 0
+        tr.write_point(params.commit(_kate_division(B, z)))
+    if opening_out is not None:
+        opening_out.update(scheme="gwc", points=[z for z, _ in groups], groups=[[q[0] for q in members] for _, members in groups])
+    return [v]
+
+
+def create_proof(params: Params, keys: Keys, advice, instances, rng: np.random.Generator, require_satisfied: bool = True, multiopen: str = "shplonk",
+                 challenges_out: list | None = None, opening_out: dict | None = None) -> bytes:
     """One circuit, every column in the caller's hands: create_proof_multi over [advice], [instances] without a callback.  advice: cs.num_advice_columns lists of n
     canonical ints (rows past the usable ones are overwritten with blinding); instances: lists of canonical ints."""
-    return create_proof_multi(params, keys, [advice], [instances], rng, require_satisfied=require_satisfied)
+    return create_proof_multi(params, keys, [advice], [instances], rng, require_satisfied=require_satisfied, challenges_out=challenges_out, multiopen=multiopen,
+                              opening_out=opening_out)
 
 
 def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng: np.random.Generator, next_phase=None, require_satisfied: bool = True,
-                       challenges_out: list | None = None) -> bytes:
+                       challenges_out: list | None = None, multiopen: str = "shplonk", opening_out: dict | None = None) -> bytes:
     """halo2's create_proof(params, pk, &[c0, c1, ..], &[inst0, inst1, ..], rng, transcript): ONE proof over m = len(advices) circuits that share the key, their advice
     committed in the phases cs.advice_column_phase names, cs.challenge_phase's user challenges squeezed between them.
     advices[c]: circuit c's cs.num_advice_columns lists of n canonical ints; the entries of later-phase columns are ignored (None will do): once the challenges of phase
@@ -291,13 +332,16 @@ def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng:
     cs.challenge_phase entry, 0 where not squeezed yet).  instances_list[c]: circuit c's lists of canonical ints.  Returns the proof bytes (Blake2b transcript).
     require_satisfied = False: behave as halo2 does on a witness that violates a gate — no check, extended_to_coeff silently truncates h(X) to (d-1) n coefficients
     (poly/domain.rs) — instead of stopping (differential tests on random circuits).  challenges_out receives every value squeezed: the user challenges in index order,
-    then theta, beta, gamma, y, x, SHPLONK's y, v, u.
+    then theta, beta, gamma, y, x, and SHPLONK's y, v, u or (multiopen = "gwc") GWC's v alone.  multiopen: "shplonk" (ProverSHPLONK) or "gwc" (ProverGWC) over the same
+    query list; opening_out receives what the argument made of the queries, named by their keys: GWC {"scheme", "points": the groups' points in group order, "groups":
+    the keys of every group's queries in order}, SHPLONK {"scheme", "sets": [(the set's points ascending, the keys of its polynomials)]}.
     Every Fr::random of halo2's provers is drawn in place, including the Blind each commitment draws (`blind()` below: drawn and dropped, as KZG does).  Wherever halo2
     loops over the circuits it does so in order 0 .. m-1 and finishes circuit c before circuit c + 1; the vanishing argument, the fixed and the sigma columns exist once."""
 
     def blind(times=1):                                              # `Blind(Scheme::Scalar::random(&mut rng))`: the stream advances, the value is unused under KZG
         for _ in range(times):
             rand_fr(rng, 1)
+    assert multiopen in ("shplonk", "gwc"), multiopen
     cs, k, n = keys.cs, params.k, params.n
     m = len(advices)
     assert m >= 1 and len(instances_list) == m
@@ -534,7 +578,7 @@ def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng:
     evals = [_poly_eval(poly, pt) for _, poly, pt in Q]
     for e in evals[:-1]:
         tr.write_scalar(e)
-    # 9: ProverSHPLONK — queries in the multi-open order: per circuit its advice, permutation and lookup queries; then fixed, sigma, h and the random polynomial once ----
+    # 9: ProverSHPLONK or ProverGWC — queries in the multi-open order: per circuit its advice, permutation and lookup queries; then fixed, sigma, h and the random polynomial once ----
     it = iter([(key, poly, pt, e) for (key, poly, pt), e in zip(Q, evals)])
     take = lambda: next(it)
     q_adv = [[take() for _ in cs.advice_queries()] for _ in circuits]
@@ -561,6 +605,11 @@ def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng:
     for c in circuits:
         queries += q_adv[c] + q_perm[c] + q_lk[c]
     queries += q_fix + q_sig + [q_h, q_rand]
+    if multiopen == "gwc":
+        tail = _gwc_multiopen(tr, params, queries, n, opening_out)
+        if challenges_out is not None:
+            challenges_out.extend(challenges + [theta, beta, gamma, y, x] + tail)
+        return bytes(tr.out)
     yy = tr.squeeze()
     super_points = sorted({q[2] for q in queries})
     order, info = [], {}
@@ -613,6 +662,8 @@ def create_proof_multi(params: Params, keys: Keys, advices, instances_list, rng:
     zt = vanish(super_points, u)
     lx = [(c_ - zt * hv) % R * z0_inv % R for c_, hv in zip(lx, h_x)]
     tr.write_point(params.commit(padn(_kate_division(lx, u))))
+    if opening_out is not None:
+        opening_out.update(scheme="shplonk", sets=[(pts, list(ks)) for pts, ks in sets])
     if challenges_out is not None:
         challenges_out.extend(challenges + [theta, beta, gamma, y, x, yy, v, u])
     return bytes(tr.out)

@@ -84,7 +84,8 @@ def seeded(seed):
 
 
 # ---- the 32-byte words of one proof, by name (§2c transcript order; §2e for the advice commitments) -------------------------------------------------------------------
-def transcript_items(cs, m):
+def transcript_items(cs, m, multiopen="shplonk"):
+    """multiopen = "gwc": the items up to the last evaluation; the words after them are the W_i, one per opening point (same_proof names them by their number)"""
     A, L, S = cs.num_advice_columns, len(cs.lookups), pc.n_sets(cs)
     phase_of, _ = phase_lists(cs)
     out = []
@@ -106,20 +107,22 @@ def transcript_items(cs, m):
     for c in range(m):
         for j in range(L):
             out += ["lookup evaluation: circuit %d, lookup %d, %s" % (c, j, what) for what in ("z", "z_next", "a", "a_inv", "s")]
-    return out + ["SHPLONK h1", "SHPLONK h2"]
+    return out + (["SHPLONK h1", "SHPLONK h2"] if multiopen == "shplonk" else [])
 
 
-def same_proof(got, want, cs, m, who):
+def same_proof(got, want, cs, m, who, multiopen="shplonk"):
     """byte equality; on a mismatch the first differing 32-byte word and the transcript item it is"""
     if got != want:
         word = pc.first_difference(got, want)
-        items = transcript_items(cs, m)
+        items = transcript_items(cs, m, multiopen)
         name = items[word] if isinstance(word, int) and word < len(items) else None
+        if multiopen == "gwc" and isinstance(word, int) and word >= len(items):
+            name = "GWC witness W_%d (group %d in order of first appearance)" % (word - len(items), word - len(items))
         raise AssertionError((who, "first differing 32-byte word", word, name))
 
 
 # ---- the reference: once per (circuit, witness, draws) in the process, shared by both backends --------------------------------------------------------------------------
-_REF = {}
+_REF, _OPENING = {}, {}
 
 
 def ints(col):
@@ -135,17 +138,23 @@ def oracle_callback(case):
     return fn
 
 
-def reference(name, k, cs, fixed, asm, key, advices, instances_list, draws, next_phase=None, satisfied=True):
-    """-> (proof bytes, squeezed challenges, the oracle's Keys) of the independent CPU prover; an item-addressed stream must end where the oracle's own order ends"""
+def reference(name, k, cs, fixed, asm, key, advices, instances_list, draws, next_phase=None, satisfied=True, multiopen="shplonk", opening=None):
+    """-> (proof bytes, squeezed challenges, the oracle's Keys) of the independent CPU prover; an item-addressed stream must end where the oracle's own order ends.
+    multiopen = "gwc": the proof that ends with ProverGWC (cached under its own name); opening, a dict, receives what the oracle's argument made of the queries."""
     import prover as op
+    if multiopen != "shplonk":
+        name = (name, multiopen)
     if name not in _REF:
         params, keys = pc.oracle_keys(k, TAU, cs, fixed, asm, key)
-        rng, squeezed = draws(), []
+        rng, squeezed, made = draws(), [], {}
         proof = op.create_proof_multi(params, keys, [[ints(a) for a in adv] for adv in advices], instances_list, rng, next_phase=next_phase,
-                                      require_satisfied=satisfied, challenges_out=squeezed)
+                                      require_satisfied=satisfied, challenges_out=squeezed, multiopen=multiopen, opening_out=made)
         if isinstance(rng, pc.PlantedRng) and rng.pattern is None:
             rng.assert_exhausted()
         _REF[name] = (proof, squeezed, keys)
+        _OPENING[name] = made
+    if opening is not None:
+        opening.update(_OPENING[name])
     return _REF[name]
 
 

@@ -6,6 +6,8 @@ definition, MSMs on the C oracle — no product code, no kernel emulator):
     reference_exact_k9_seed3.bin  census B of the same tool (the reference's base64 sub-circuit built exactly + chip estimate), k = 9, rng 3
     toy_m2_k6_seed5.bin        ONE proof over two witnesses of the toy key (test_multi_circuit.toy_witness(6, s=c, t=2c), c = 0, 1), rng 5
     phased_{A,B,D}_k6_seed5.bin   tests/phased_cases.py: two advice phases and a challenge (A), three phases and four challenges (B), A over two circuits (D), rng 5
+    toy_gwc_k6_seed7.bin, toy_m2_gwc_k6_seed5.bin, phased_A_gwc_k6_seed5.bin, alias_eq_gwc_k5.bin   tests/gwc_cases.py GOLDENS: the toy, the two-circuit toy and
+                               phased case A again, and the aliased-rotation circuit with its equality-enabled column (alias_eq, k = 5, rng 14), ending with the GWC multi-open instead of SHPLONK
 The Fr::random draws follow halo2_proofs v2023_01_20 (incl. the Blind of every commitment).  All with the SRS trapdoor TAU of the tests.  The GPU prover (and the emulated kernels) must emit exactly these bytes, and the pure-Python
 verifier must accept them.  They are NOT outputs of the reference (no Rust toolchain here; the reference holds no stack-A proof): they replace the
 round-1 goldens, which the emulator build of the product's own kernels had produced."""
@@ -88,6 +90,16 @@ def main():
         out = os.path.join(ROOT, "tests", "golden", name)
         open(out, "wb").write(proof)
         print("wrote", out, len(proof), "bytes (CPU prover over %d circuit(s), accepted by the test-side verifier)" % len(insts))
+    # proofs that end with the GWC multi-open (create_proof_multi(.., multiopen="gwc")): the cases of tests/gwc_cases.py, accepted by tests/gwc_verifier.py
+    import gwc_cases as gc
+    import gwc_verifier as gv
+    for name, build in gc.GOLDENS:
+        case = build()
+        proof, _, keys = gc.reference(case)
+        assert gv.verify_proof_gwc(keys, gc.TAU, case.instances_list, proof) is True, name
+        out = os.path.join(ROOT, "tests", "golden", name)
+        open(out, "wb").write(proof)
+        print("wrote", out, len(proof), "bytes (CPU prover, GWC multi-open over %d circuit(s), accepted by the test-side GWC verifier)" % case.m)
 
 
 if __name__ == "__main__":
